@@ -15,6 +15,11 @@ Workload (BASELINE.json north_star target, configs[3] geometry on ONE GPU per ra
   Rank r owns the contiguous realization range [r*K*batch, (r+1)*K*batch) ("weak" scaling); the only
   exchange is ONE all-reduce (RCCL) of the 6-word integer counter vector, inside the timed region.
 
+A plain run sets up, warms up, times the K steps of the headline (--config / --dtype / --demod), writes the timed path's
+outputs if --dump-outputs DIR is given, and prints the line.  `--full` adds every other leg: the other arithmetic and
+demodulator, the CPU baselines of the NumPy oracle and the SER check against them, live rocprofv3 counters, the other
+workloads, the staged HBM legs, and in a multi-rank run the rank-0-alone and strong-scaling legs.
+
 `--launch-check` exercises the launcher, the range split and the reduction WITHOUT a GPU (gloo, an integer
 checksum per realization index instead of a kernel; no rate is reported) -- tests/test_bench_launch.py.
 """
@@ -234,21 +239,29 @@ def parse():
                     help="print the bench arguments of profile tag TAG (or 'list': every tag) and exit: scripts/prof_r06.sh")
     ap.add_argument("--config", default="c4", choices=["c2", "c3", "c4", "c5", "f1", "f6"])
     ap.add_argument("--batch", type=int, default=0, help="realizations per GPU per step")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg besides the headline (see the module docstring); without it only the --demod / --dtype "
+                         "combination is timed and nothing else is measured")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed (its counters, and the per-realization "
+                         "error counts of its last step) as DIR/<name>.npy in float32 / float64")
     ap.add_argument("--single-demod", action="store_true",
-                    help="time only the --demod / --dtype combination (profiling runs: every launch is then the same kernel work)")
+                    help="with --full: time only the --demod / --dtype combination (profiling runs: every launch is then the "
+                         "same kernel work); a plain run always does")
     ap.add_argument("--demod", default="mindist", choices=["slicer", "mindist"],
                     help="demodulator `value` is quoted on (mindist = the north star's min-distance search over the LDS "
-                         "constellation table); the c4 line carries the rate of both")
+                         "constellation table); a --full c4 line carries the rate of both")
     ap.add_argument("--dtype", default="f64", choices=["f32", "f64"],
-                    help="arithmetic `value` is quoted on: f64 = complex128, the reference's own precision (default); the "
-                         "line carries the complex64 rate of the same workload next to it (dtype_rates)")
+                    help="arithmetic `value` is quoted on: f64 = complex128, the reference's own precision (default); a "
+                         "--full line carries the complex64 rate of the same workload next to it (dtype_rates)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the cpu_baseline leg")
     ap.add_argument("--cpu-multicore-seconds", type=float, default=6.0,
                     help="budget of the all-cores CPU leg (0 disables it)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU legs and the other-workload survey")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU legs and the other-workload survey")
     ap.add_argument("--pmc", default="auto", choices=["auto", "on", "off"],
-                    help="collect the VALU / MFMA / HBM counters of the dominant kernel with rocprofv3 child runs "
-                         "(auto: single rank, rocprofv3 on PATH, CPU legs not disabled)")
+                    help="with --full: collect the VALU / MFMA / HBM counters of the dominant kernel with rocprofv3 child runs "
+                         "(auto: single rank, rocprofv3 on PATH, CPU legs not disabled); a plain run quotes the committed "
+                         "summary")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="kernel-selection option of the context (mcle_ctx_set_option; names: pyphysim_amd._lib.OPTIONS), "
                          "e.g. --opt no_mfma=1 --opt grid_oversub=4; repeatable, for A/B runs")
@@ -265,7 +278,7 @@ def parse():
                     help="rank r uses GPU r mod (visible GPUs) instead of failing when there are fewer GPUs than ranks "
                          "(tests of the N > 1 path on one GPU, together with --dist-backend gloo; never a scaling figure)")
     ap.add_argument("--strong-total", type=int, default=0,
-                    help="total realizations of the strong-scaling leg of a multi-rank run (0: BASELINE.json's literal count "
+                    help="total realizations of the strong-scaling leg of a multi-rank --full run (0: BASELINE.json's literal count "
                          "for the configuration: config 4 1e6, config 5 1e5); split contiguously over the ranks")
     ap.add_argument("--strong-reps", type=int, default=5, help="timed repetitions of the strong-scaling leg (median reported)")
     ap.add_argument("--launch-check", action="store_true",
@@ -304,7 +317,8 @@ def self_launch(args):
 
 # ---- workloads --------------------------------------------------------------------------------------------------
 def make_runner(eng, cfg, demod, dtype):
-    """-> (run(first, count, counters), units per realization, description)"""
+    """-> (run(first, count, counters, **kw), units per realization, description); run returns what the engine call returns
+    (nothing into `counters`; with counters=None, per_realization=True: the counter dict, symbol and bit errors per realization)"""
     from pyphysim_amd.modulators import constellation  # product-side tables (no oracle import here)
     from pyphysim_amd import _lib
     method = _lib.DEMOD_QAM_SLICER if demod == "slicer" else _lib.DEMOD_MINDIST
@@ -312,49 +326,49 @@ def make_runner(eng, cfg, demod, dtype):
     if cfg == "c4":
         eng.set_constellation(constellation("qam", 64), _lib.CONST_QAM)
 
-        def run(first, count, counters):
-            eng.run_mimo_ofdm(4, 4, 1024, 16, 1024, 1, nv, SEED, first, count, mmse=True, method=method,
-                              dtype=dtype, counters=counters)
+        def run(first, count, counters, **kw):
+            return eng.run_mimo_ofdm(4, 4, 1024, 16, 1024, 1, nv, SEED, first, count, mmse=True, method=method,
+                                     dtype=dtype, counters=counters, **kw)
         return run, 4096, "4x4 Blast-MMSE + 64-QAM + OFDM(1024, cp 16), flat randn_c H, SNR 25 dB (config 4)"
     if cfg == "c2":
         eng.set_constellation(constellation("qam", 64), _lib.CONST_QAM)
 
-        def run(first, count, counters):
-            eng.run_flat_fading(100000, nv, SEED, first, count, Fd=100.0, Ts=1e-3, L=8, method=method, dtype=dtype,
-                                counters=counters)
+        def run(first, count, counters, **kw):
+            return eng.run_flat_fading(100000, nv, SEED, first, count, Fd=100.0, Ts=1e-3, L=8, method=method, dtype=dtype,
+                                       counters=counters, **kw)
         return run, 100000, "64-QAM over flat Jakes fading (Fd 100 Hz, Ts 1 ms, L 8), 1e5 symbols, SNR 20 dB (config 2)"
     if cfg == "f1":
         eng.set_constellation(constellation("qam", 64), _lib.CONST_QAM)
         from pyphysim_amd.channels import discretize_profile
         p_lin, d_idx = discretize_profile(np.array(F1_TAPS_DB), np.arange(5) * F1_TS, F1_TS)
 
-        def run(first, count, counters):
-            eng.run_mimo_ofdm_tdl(4, 4, 1024, 16, 1024, 1, nv, p_lin, d_idx, SEED, first, count, Fd=10.0, Ts=F1_TS,
-                                  L=8, mmse=True, method=method, dtype=dtype, counters=counters)
+        def run(first, count, counters, **kw):
+            return eng.run_mimo_ofdm_tdl(4, 4, 1024, 16, 1024, 1, nv, p_lin, d_idx, SEED, first, count, Fd=10.0, Ts=F1_TS,
+                                         L=8, mmse=True, method=method, dtype=dtype, counters=counters, **kw)
         return run, 4096, ("4x4 MMSE per subcarrier + 64-QAM + OFDM(1024, cp 16) over a 5-tap Jakes MIMO TDL channel "
                            "(Fd 10 Hz), SNR 25 dB (SURVEY 8(f).1)")
     if cfg == "f6":
         eng.set_constellation(constellation("psk", 4), _lib.CONST_GENERIC)
 
-        def run(first, count, counters):
-            eng.run_bd(3, 2, 500, 1.0, nv, SEED, first, count, method=_lib.DEMOD_MINDIST, dtype=dtype,
-                       counters=counters)
+        def run(first, count, counters, **kw):
+            return eng.run_bd(3, 2, 500, 1.0, nv, SEED, first, count, method=_lib.DEMOD_MINDIST, dtype=dtype,
+                              counters=counters, **kw)
         return run, 3000, ("K=3 cells of 2x2 antennas, block-diagonalising precoder (water-filling) + zero forcing, "
                            "4-PSK, 500 symbols/stream, SNR 15 dB (apps/comp_BD/simulate_comp_simple.py; SURVEY 8(f).3)")
     if cfg == "c5":
         eng.set_constellation(constellation("qam", 16), _lib.CONST_QAM)
 
-        def run(first, count, counters):
-            eng.run_ia(200, nv, SEED, first, count, method=method, dtype=dtype, counters=counters)
+        def run(first, count, counters, **kw):
+            return eng.run_ia(200, nv, SEED, first, count, method=method, dtype=dtype, counters=counters, **kw)
         return run, 600, "K=3 2x2 closed-form interference alignment + 16-QAM, 200 symbols/stream, SNR 20 dB (config 5)"
     eng.set_constellation(constellation("qpsk", 4), _lib.CONST_GENERIC)
     from pyphysim_amd.channels import discretize_profile
     Ts = 1.0 / (15e3 * 1024)
     p_lin, d_idx = discretize_profile(np.array([0.0, -3.0, -6.0, -9.0, -12.0]), np.arange(5) * Ts, Ts)
 
-    def run(first, count, counters):
-        eng.run_ofdm_tdl(1024, 16, 1024, 1, nv, p_lin, d_idx, SEED, first, count, Fd=10.0, Ts=Ts, L=8,
-                         method=_lib.DEMOD_MINDIST, dtype=dtype, counters=counters)
+    def run(first, count, counters, **kw):
+        return eng.run_ofdm_tdl(1024, 16, 1024, 1, nv, p_lin, d_idx, SEED, first, count, Fd=10.0, Ts=Ts, L=8,
+                                method=_lib.DEMOD_MINDIST, dtype=dtype, counters=counters, **kw)
     return run, 1024, "QPSK + OFDM(1024, cp 16) over 5-tap Jakes TDL (Fd 10 Hz), one-tap EQ, SNR 20 dB (config 3)"
 
 
@@ -726,6 +740,46 @@ def launch_check(args, rank, world):
     dist.destroy_process_group()
 
 
+# ---- --dump-outputs ---------------------------------------------------------------------------------------------
+DUMP_MAX_REALIZATIONS = 1 << 21     # per-realization arrays of a larger step: a fixed sample of this many (seeded by SEED)
+
+
+def dump_outputs(folder, run, first, count, timed_tot):
+    """What the timed path computed, as DIR/<name>.npy (same arguments, same files: every draw is keyed by (SEED, realization)):
+      timed_counters            float64, COUNTER_KEYS summed over the K timed steps (and the ranks), as the line's ser / ber
+      last_step_counters        float64, every field of the counter block (pyphysim_amd._lib.COUNTER_FIELDS) of the last step
+      last_step_symbol_errors   float32, per realization of the last step (-1: realization skipped), exact below 2^24
+      last_step_bit_errors      float32, the same for bits
+      last_step_capacities      float64, config 5 only: the sum capacity per realization
+      last_step_sample_index    float64, only when the step has more than DUMP_MAX_REALIZATIONS: the realization indices kept
+    The last step is launched once more after the clock stopped, the same call with per-realization outputs requested; its
+    counters must equal the sums of those outputs.  At most 2^21 x (4 + 4 + 8 + 8) bytes = 48 MiB in all."""
+    from pyphysim_amd import _lib
+    got = run(first, count, None, per_realization=True)
+    res = got[0]
+    se, be = np.asarray(got[1]).astype(np.int64), np.asarray(got[2]).astype(np.int64)
+    skipped = se == 0xFFFFFFFF
+    se[skipped] = -1
+    be[skipped] = -1
+    if int(se[~skipped].sum()) != res["sym_errors"] or int(be[~skipped].sum()) != res["bit_errors"]:
+        raise SystemExit("bench.py: the last step's per-realization errors do not add up to its counters")
+    if max(int(se.max()), int(be.max())) >= 1 << 24:
+        raise SystemExit("bench.py: per-realization error counts beyond float32's exact range")
+    arrays = {"timed_counters": np.array(timed_tot, dtype=np.float64),
+              "last_step_counters": np.array([res[k] for k in _lib.COUNTER_FIELDS], dtype=np.float64)}
+    keep = slice(None)
+    if count > DUMP_MAX_REALIZATIONS:
+        keep = np.sort(np.random.default_rng(SEED).choice(count, DUMP_MAX_REALIZATIONS, replace=False))
+        arrays["last_step_sample_index"] = (first + keep).astype(np.float64)
+    arrays["last_step_symbol_errors"] = se[keep].astype(np.float32)
+    arrays["last_step_bit_errors"] = be[keep].astype(np.float32)
+    if len(got) > 3:
+        arrays["last_step_capacities"] = np.asarray(got[3], dtype=np.float64)[keep]
+    os.makedirs(folder, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(folder, name + ".npy"), arr)
+
+
 # ---- main -------------------------------------------------------------------------------------------------------
 def main():
     args = parse()
@@ -747,6 +801,8 @@ def main():
         raise SystemExit("bench.py: --gpus %d but WORLD_SIZE=%d (launch one rank per GPU)" % (args.gpus, world))
     if args.launch_check:
         return launch_check(args, rank, world)
+    if args.pmc == "on" and not args.full:
+        raise SystemExit("bench.py: --pmc on needs --full (live counters are rocprofv3 runs of their own)")
     from pyphysim_amd.engine import Engine   # loads libmcle (shares torch's HIP runtime)
     import torch
     import torch.distributed as dist
@@ -948,9 +1004,12 @@ def main():
     head = timed(args.demod, args.dtype, 0)
     elapsed, kernel_ms, tot, workload, units = head["elapsed"], head["kernel_ms"], head["tot"], head["workload"], head["units"]
     n_real = tot[0] + tot[1]
-    # the same workload in the other arithmetic and with the other demodulator, each timed exactly like the headline
+    if args.dump_outputs and rank == 0:     # rank 0's last timed step: [(K - 1) batch, K batch) of its range
+        dump_outputs(args.dump_outputs, make_runner(eng, args.config, args.demod, args.dtype)[0], (args.steps - 1) * batch,
+                     batch, tot)
+    # --full: the same workload in the other arithmetic and with the other demodulator, each timed exactly like the headline
     rates = {args.dtype: {args.demod: head}}
-    if not args.single_demod:
+    if args.full and not args.single_demod:
         base_i = 1
         for dt in (args.dtype, "f32" if args.dtype == "f64" else "f64"):
             for dm in ((args.demod, "slicer" if args.demod == "mindist" else "mindist") if args.config == "c4" else (args.demod,)):
@@ -958,9 +1017,9 @@ def main():
                     continue
                 rates.setdefault(dt, {})[dm] = timed(dm, dt, base_i << 36)
                 base_i += 1
-    solo = timed(args.demod, args.dtype, 15 << 36, solo=True) if world > 1 else None
+    solo = timed(args.demod, args.dtype, 15 << 36, solo=True) if world > 1 and args.full else None
     strong = None
-    if use_dist and args.strong_reps > 0:
+    if args.full and use_dist and args.strong_reps > 0:
         s_total = args.strong_total or STRONG_TOTAL[args.config]
         s_all = timed_strong(args.demod, args.dtype, s_total, 17 << 36)
         s_one = timed_strong(args.demod, args.dtype, s_total, 18 << 36, solo=True) if world > 1 else s_all
@@ -1009,7 +1068,7 @@ def main():
 
     if rank == 0:
         value = n_real / elapsed
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             try:
                 sys.path.insert(0, os.path.join(REPO, "scripts"))
                 import bench_staged_c4
@@ -1023,7 +1082,7 @@ def main():
             batch: the counters are normalised per realization), else the committed summary"""
             per_launch_s = res["kernel_ms_per_launch"] * 1e-3
             pmc, src, pmc_batch = None, None, None
-            want = args.pmc == "on" or (args.pmc == "auto" and world == 1 and not args.no_cpu)
+            want = args.full and (args.pmc == "on" or (args.pmc == "auto" and world == 1 and not args.no_cpu))
             if want:
                 eng.sync()
                 pmc_batch = min(batch, BATCH_SURVEY[args.config] * 4)
@@ -1049,7 +1108,7 @@ def main():
         out = {
             "metric": "Monte Carlo realizations/sec (whole node) + SER abs-error vs ref",
             "value": value, "unit": "realizations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "preroll_ms": args.preroll_ms,
+            "preroll_ms": args.preroll_ms, "full": args.full,
             "ms_per_step": elapsed * 1e3 / args.steps, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
             "value_is": "%s arithmetic (%s), %s demodulator" % (
@@ -1088,6 +1147,7 @@ def main():
             out["strong_c5"] = strong_c5
         if world > 1:
             out["kernel_ms_per_rank"] = {"min": head["kernel_ms_min"], "max": head["kernel_ms"]}
+        if solo is not None:
             out["n1_value"] = solo["rate"]
             out["n1_note"] = ("rank 0 alone, same job, same K steps and batch, the other ranks holding the barriers; "
                               "value / (n_gpus * n1_value) = %.4f" % (value / (world * solo["rate"])))
@@ -1099,7 +1159,7 @@ def main():
             if dm != args.demod:
                 out[dm + "_demod_realizations_per_s"] = r["rate"]
                 out[dm + "_demod_kernel_ms_per_launch"] = r["kernel_ms_per_launch"]
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             # per-realization counts of the first realizations for the SER cross-check
             res, se, be = eng_first_counts(eng, args, 16384 if args.config != "c2" else 128)
             cb, ser_err, n_chk = cpu_baseline(args.config, args.cpu_seconds, se)

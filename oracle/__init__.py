@@ -5,7 +5,7 @@ reference's per-realization chain.  Each function cites t
 reference file:line it follows (paths relative to the reference checkout).
 
 Who may import it: ``tests/``, ``__graft_entry__.smoke()`` and the
-``cpu_baseline`` leg of ``bench.py`` -- as the *checker* / reported baseline,
+``cpu_baseline`` leg of ``bench.py --full`` -- as the *checker* / reported baseline,
 never as the thing measured or shipped.  Nothing under ``pyphysim_amd/``
 imports it; the product path fails loudly when the HIP library is missing.
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Condense gpurun_out/ (rocprofv3 csv + bench json) into the tracked profiles/<round>/ summaries.
 
-usage: python scripts/collect_profiles.py r02
+usage: python scripts/collect_profiles.py r02 [FOLDER]   (FOLDER: the runs' outputs, e.g. gpu_check_out from scripts/gpu_check.sh)
 For every profiled config (c4, c3, c2, f1, c5, f6) writes <cfg>_kernel_stats.csv and <cfg>_pmc_summary.json
 (round 5: counter SUMS over every dispatch of the dominant kernel in the counter run + the realizations those dispatches
 cover (`_realizations_total` = (warm-up + timed steps) x batch) + the `_derived` fractions of bench.derive_pmc, the same
@@ -26,6 +26,8 @@ rnd = sys.argv[1] if len(sys.argv) > 1 else "r06"
 sys.path.insert(0, REPO)
 from bench import derive_pmc  # noqa: E402
 src = os.path.join(REPO, "gpurun_out")
+if len(sys.argv) > 2:
+    src = os.path.abspath(sys.argv[2])
 dst = os.path.join(REPO, "profiles", rnd)
 os.makedirs(dst, exist_ok=True)
 

@@ -103,3 +103,12 @@ def test_profile_table_matches_the_bench_legs():
                                                           str(bench.BATCH_SURVEY["c2"])]
     script = open(os.path.join(REPO, "scripts", "prof_r06.sh")).read()
     assert "--profile-spec" in script and "--batch" not in script.replace("--batch of", "")
+
+
+def test_live_counters_are_a_full_run_leg():
+    """A plain run times the headline and nothing else: live rocprofv3 counters (child runs of their own) need --full, and the
+    refusal comes before any GPU work."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "1", "--pmc", "on"], env=env,
+                         capture_output=True, text=True, timeout=120)
+    assert out.returncode != 0 and "--full" in out.stderr and not [l for l in out.stdout.splitlines() if l.startswith("{")]

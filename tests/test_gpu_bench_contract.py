@@ -1,6 +1,7 @@
 """GPU: the driver's contract on bench.py's ONE JSON line (N = 1, no launcher): the metric of BASELINE.json on the config-4
-workload, value in complex128 with the north star's demodulator, both dtypes' rates, the roofline block of the dominant
-kernel, the CPU baseline of the NumPy oracle, the staged HBM leg -- on a reduced batch so that the test takes seconds."""
+workload, value in complex128 with the north star's demodulator; with --full both dtypes' rates, the roofline block of the
+dominant kernel, the CPU baseline of the NumPy oracle, the staged HBM leg -- on a reduced batch so that the test takes seconds.
+A plain run times the headline alone and, with --dump-outputs, writes what its timed path computed."""
 import json
 import os
 import subprocess
@@ -15,7 +16,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.timeout(900)
 def test_default_line_carries_every_contract_field():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "16384",
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--batch", "16384",
                           "--cpu-seconds", "1", "--cpu-multicore-seconds", "0", "--pmc", "off", "--preroll-ms", "0"],
                          env=env, capture_output=True, text=True, timeout=800)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -78,3 +79,50 @@ def test_default_line_carries_every_contract_field():
         f1 = d["other_workloads"]["f1"][dt]
         assert 0.0 < f1["flop_frac_survey_model"] < f1["flop_frac"] < 1.0
     assert d["roofline"]["valu_busy_chip"] is None or 0.0 < d["roofline"]["valu_busy_chip"] <= 1.0
+
+
+@pytest.mark.timeout(600)
+def test_plain_line_times_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """No --full: the contract fields on the headline alone (no other leg ran), and --dump-outputs writes what the timed path
+    computed -- the same files on a second run (every draw is keyed by seed and realization index), the last step's counts
+    equal to the NumPy oracle's on its first realizations (complex128, min-distance: exact)."""
+    import numpy as np
+    from oracle import chains
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    batch, steps = 16384, 3
+
+    def bench(folder):
+        out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", str(steps), "--warmup", "1",
+                              "--batch", str(batch), "--preroll-ms", "0", "--dump-outputs", str(folder)],
+                             env=env, capture_output=True, text=True, timeout=500)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+
+    d = bench(tmp_path / "a")
+    base = json.load(open(os.path.join(REPO, "BASELINE.json")))
+    assert d["metric"] == base["metric"] and d["unit"] == "realizations/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f64" and d["config"]["demod"] == "mindist" and d["full"] is False and d["steps"] == steps
+    assert d["value"] > 1e6 and abs(d["value"] - batch / d["ms_per_step"] * 1e3) <= 1e-6 * d["value"]
+    assert d["rates"] == {"f64": {"mindist": d["value"]}}
+    for key in ("cpu_baseline", "ser_abs_err_vs_oracle", "other_workloads", "roofline_f32", "hbm_copy_GBps_measured_this_run",
+                "slicer_demod_realizations_per_s", "strong", "n1_value"):
+        assert key not in d, key
+    names = {"timed_counters", "last_step_counters", "last_step_symbol_errors", "last_step_bit_errors"}
+    assert {p.name for p in (tmp_path / "a").iterdir()} == {n + ".npy" for n in names}
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    tc, last = got["timed_counters"], got["last_step_counters"]
+    assert tc.dtype == np.float64 and tc[0] + tc[1] == steps * batch and tc[2] / (tc[0] * 4096) == d["ser"]
+    se, be = got["last_step_symbol_errors"], got["last_step_bit_errors"]
+    assert se.dtype == be.dtype == np.float32 and se.shape == be.shape == (batch,)
+    assert last[0] == batch and se.astype(np.int64).sum() == last[2] and be.astype(np.int64).sum() == last[4] <= tc[4]
+    first = (steps - 1) * batch                                            # the last timed step's realization indices
+    kw = dict(mod="qam", M=64, nt=4, nr=4, fft_size=1024, cp_size=16, num_used=None, n_ofdm_sym=1, snr_db=25.0, mmse=True)
+    for r in range(3):
+        want = chains.chain_mimo_ofdm(chains.PhiloxRng(20260927, first + r), **kw)
+        assert (se[r], be[r]) == (want["symbol_errors"], want["bit_errors"]), r
+    d2 = bench(tmp_path / "b")
+    assert d2["ser"] == d["ser"] and d2["ber"] == d["ber"]
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "b" / (n + ".npy")), got[n]), n

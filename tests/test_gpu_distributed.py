@@ -170,7 +170,7 @@ def test_bench_under_the_drivers_launch_line_runs_the_rccl_allreduce():
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4096", "--no-cpu", "--pmc", "off",
+    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4096", "--full", "--no-cpu", "--pmc", "off",
               "--preroll-ms", "0", "--single-demod"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
@@ -219,7 +219,7 @@ def test_bench_two_rank_code_path_on_one_gpu():
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    common = ["--warmup", "1", "--batch", "4096", "--no-cpu", "--pmc", "off", "--preroll-ms", "0", "--single-demod"]
+    common = ["--warmup", "1", "--batch", "4096", "--full", "--no-cpu", "--pmc", "off", "--preroll-ms", "0", "--single-demod"]
     two = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "2", "--dist-backend", "gloo",
                           "--share-gpus", "--strong-total", "20000", "--strong-reps", "2"] + common, env=env, capture_output=True, text=True, timeout=800)
     assert two.returncode == 0, two.stderr[-3000:]
@@ -255,7 +255,7 @@ def test_bench_eight_rank_code_path_on_one_gpu():
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    common = ["--warmup", "1", "--no-cpu", "--pmc", "off", "--preroll-ms", "0", "--single-demod", "--dist-backend", "gloo",
+    common = ["--warmup", "1", "--full", "--no-cpu", "--pmc", "off", "--preroll-ms", "0", "--single-demod", "--dist-backend", "gloo",
               "--strong-total", "20001", "--strong-reps", "1"]
     eight = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "8", "--steps", "1", "--batch", "2048",
                             "--share-gpus"] + common, env=env, capture_output=True, text=True, timeout=1400)
