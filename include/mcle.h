@@ -73,6 +73,11 @@ int mcle_ctx_sync(mcle_ctx* ctx);
  * Waits for the stream first.  The next call that needs it allocates again. */
 int mcle_ctx_trim_scratch(mcle_ctx* ctx);
 int mcle_ctx_device_info(mcle_ctx* ctx, int* n_cu, int* lds_bytes, char* name, int name_len);
+/* Diagnostic: a short tag naming the kernel that served the context's last mcle_run_ofdm_tdl / mcle_run_mimo_ofdm_tdl call, e.g.
+ * "siso_hw K=3", "siso_wave N=1024 K=6", "siso_batched K=9", "siso_mfma", "siso_single", "mimo_wave_parked K=5", "mimo_wave_rt K=3",
+ * "mimo_coop" (K: the tap polynomials' order).  Empty before such a call and after one that launched nothing.  Copies at most
+ * len - 1 characters and a terminating zero into name. */
+int mcle_ctx_last_kernel(mcle_ctx* ctx, char* name, int len);
 int mcle_malloc(mcle_ctx* ctx, size_t bytes, void** d_ptr);
 int mcle_free(mcle_ctx* ctx, void* d_ptr);
 int mcle_memset(mcle_ctx* ctx, void* d_ptr, int value, size_t bytes);
@@ -493,10 +498,19 @@ int mcle_run_awgn(mcle_ctx* ctx, int dtype, const mcle_awgn_cfg* cfg, uint64_t s
  * complex products: <= 3e-15 relative drift against evaluating sin / cos at every sample, which is what NumPy does).  The
  * per-realization error counts equal the oracle's on every tested case incl. the full 10^5-symbol config 2, but that is by
  * test coverage, not by construction: a symbol within 3e-15 of a decision boundary may flip.  MCLE_OPT_JAKES_DIRECT = 1
- * evaluates every sample (the literal parity statement, 3.3 x slower). */
+ * evaluates every sample (the literal parity statement, 3.3 x slower).  Fd may have either sign (as in the reference) and must be
+ * finite. */
 int mcle_run_flat_fading(mcle_ctx* ctx, int dtype, const mcle_flat_cfg* cfg, uint64_t seed,
                          uint64_t first, uint64_t count, mcle_counters* d_counters,
                          uint32_t* d_sym_err, uint32_t* d_bit_err);
+/* Config 3.  Fd may have either sign (as in the reference's JakesSampleGenerator; the kernels use |Fd| wherever they choose by
+ * it) and must be finite.  Kernel chain (mcle_ctx_last_kernel names the one that ran): at 2048 points the two-wavefront kernel takes
+ * every delay inside the prefix at polynomial orders 2 .. 5; a delay beyond the prefix (dmax > cp_size) falls back to the
+ * one-wavefront kernel, which takes <= 8 taps reaching <= min(256, fft_size / 2) samples back at orders 2 .. 5 (2 .. 8 at 1024);
+ * then the batched kernels (orders <= 12, delays < fft_size; complex64 at 1024 with every delay inside the prefix: the matrix-core
+ * kernel first), then the one-realization-per-workgroup kernel.  All of them give the same counts (complex128: exactly).
+ * complex64 counts can change with n_ofdm_sym alone: the quarter-turn rule at mcle_run_mimo_ofdm_tdl counts every symbol of the
+ * run, so adding symbols can move the rays' frequencies from float to double for the symbols already there. */
 int mcle_run_ofdm_tdl(mcle_ctx* ctx, int dtype, const mcle_ofdm_tdl_cfg* cfg, uint64_t seed,
                       uint64_t first, uint64_t count, mcle_counters* d_counters,
                       uint32_t* d_sym_err, uint32_t* d_bit_err);
@@ -522,7 +536,9 @@ int mcle_run_mimo_flat(mcle_ctx* ctx, int dtype, const mcle_mimo_flat_cfg* cfg, 
  * (mcle_run_ofdm_tdl: at most 2 GiB) -- and is kept until the context is destroyed.
  * complex64 (this function and mcle_run_ofdm_tdl): while the largest Doppler phase of the run, Fd x (Ts + dt x samples of all symbols),
  * stays below a quarter turn the rays' Doppler frequencies are evaluated in float (v_cos_f32: < 4e-7 turns of phase, below the float
- * phasor's own rounding); beyond that in double as in complex128. */
+ * phasor's own rounding); beyond that in double as in complex128.  The threshold counts every symbol of the run, so complex64 counts
+ * of the first symbols can change with n_ofdm_sym across it (within the complex64 tolerance of the oracle on both sides).
+ * Fd must be >= 0 here (MCLE_E_INVAL otherwise; mcle_run_ofdm_tdl takes either sign). */
 int mcle_run_mimo_ofdm_tdl(mcle_ctx* ctx, int dtype, const mcle_mimo_ofdm_tdl_cfg* cfg, uint64_t seed,
                            uint64_t first, uint64_t count, mcle_counters* d_counters,
                            uint32_t* d_sym_err, uint32_t* d_bit_err);

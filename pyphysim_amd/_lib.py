@@ -140,6 +140,7 @@ _PROTOS = {
     "mcle_ctx_set_option": (c_int, [_P, c_int, c_longlong]),
     "mcle_ctx_get_option": (c_int, [_P, c_int, POINTER(c_longlong)]),
     "mcle_ctx_device_info": (c_int, [_P, POINTER(c_int), POINTER(c_int), c_char_p, c_int]),
+    "mcle_ctx_last_kernel": (c_int, [_P, c_char_p, c_int]),
     "mcle_malloc": (c_int, [_P, c_size_t, POINTER(_P)]),
     "mcle_free": (c_int, [_P, _P]),
     "mcle_memset": (c_int, [_P, _P, c_int, c_size_t]),

@@ -279,6 +279,13 @@ int mcle_ctx_device_info(mcle_ctx* ctx, int* n_cu, int* lds_bytes, char* name, i
     return MCLE_OK;
 }
 
+int mcle_ctx_last_kernel(mcle_ctx* ctx, char* name, int len) {
+    MCLE_REQUIRE(ctx != nullptr && name != nullptr && len > 0, "null argument");
+    std::strncpy(name, ctx->last_kernel, len - 1);
+    name[len - 1] = 0;
+    return MCLE_OK;
+}
+
 int mcle_malloc(mcle_ctx* ctx, size_t bytes, void** d_ptr) {
     MCLE_REQUIRE(ctx != nullptr && d_ptr != nullptr, "null argument");
     MCLE_HIP(hipSetDevice(ctx->device));

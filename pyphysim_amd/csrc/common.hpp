@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -255,6 +256,15 @@ struct mcle_ctx {
 
     // kernel-selection options (mcle_ctx_set_option); 0 = default
     long long opt[MCLE_OPT_COUNT] = {};
+    // which kernel served the last config-3 / f1 call (mcle_ctx_last_kernel; host-only diagnostic): cleared on entry, set where
+    // the chosen kernel launches
+    char last_kernel[48] = {};
+    void set_kernel(const char* fmt, ...) {
+        va_list ap;
+        va_start(ap, fmt);
+        std::vsnprintf(last_kernel, sizeof(last_kernel), fmt, ap);
+        va_end(ap);
+    }
 
     int bind() const;
     int get_twiddles(int n, int dtype, void** d_tw);

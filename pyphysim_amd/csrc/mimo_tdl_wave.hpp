@@ -720,6 +720,7 @@ int launch_mimo_tdl_wave(mcle_ctx* ctx, const MimoTdlParams& pp, int method, uin
     const size_t one = (size_t)per_real * sizeof(cx<T>);
     if ((rc = ctx->scratch_upto((size_t)slice * one, (slice < 64 ? slice : 64) * one, &recs, &got))) return rc;
     if (got / one < slice) slice = got / one;
+    ctx->set_kernel(KT > 0 ? "mimo_wave_parked K=%d" : "mimo_wave_rt K=%d", pp.K);
     for (uint64_t off = 0; off < count; off += slice) {
         const uint64_t n = count - off < slice ? count - off : slice;
         launch_mimo_tdl_symbol_polys<T, true>(ctx->stream, pw, PS, NR * NT, N + pp.cp, seed, first + off, n, (cx<T>*)recs, NT);

@@ -416,6 +416,7 @@ int run_mimo_tdl_impl(mcle_ctx* ctx, MimoTdlParams pp, int method, uint64_t seed
     if (slice > count) slice = count;
     void* recs = nullptr;
     if ((rc = ctx->scratch((size_t)slice * per_real * sizeof(cx<T>), &recs))) return rc;
+    ctx->set_kernel("mimo_coop");
     for (uint64_t off = 0; off < count; off += slice) {
         const uint64_t n = count - off < slice ? count - off : slice;
         launch_mimo_tdl_symbol_polys<T, false>(ctx->stream, pp, (int)PS, NA * NA, N + pp.cp, seed, first + off, n, (cx<T>*)recs, 0);
@@ -485,6 +486,7 @@ using namespace mcle;
 extern "C" int mcle_run_mimo_ofdm_tdl(mcle_ctx* ctx, int dtype, const mcle_mimo_ofdm_tdl_cfg* cfg, uint64_t seed,
                                       uint64_t first, uint64_t count, mcle_counters* d_counters,
                                       uint32_t* d_sym_err, uint32_t* d_bit_err) {
+    if (ctx) ctx->last_kernel[0] = 0;
     int rc = check_pipe(ctx, dtype, cfg ? cfg->demod_method : 0, cfg);
     if (rc) return rc;
     MCLE_REQUIRE(cfg->nt >= 1 && cfg->nt <= cfg->nr && cfg->nr <= 4,

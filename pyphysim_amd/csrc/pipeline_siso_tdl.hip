@@ -780,6 +780,7 @@ int run_siso_tdl_mfma(mcle_ctx* ctx, const SisoTdlParams& pp, int method, uint64
     if (slice > count) slice = (count + NB - 1) / NB * NB;
     void* recs = nullptr;
     if ((rc = ctx->scratch((size_t)slice * per_real * sizeof(float2), &recs))) return rc;
+    ctx->set_kernel("siso_mfma");
     for (uint64_t off = 0; off < count; off += slice) {
         const uint64_t n = count - off < slice ? count - off : slice;
         launch_tdl_symbol_polys<float>(ctx->stream, pp, kF16N + pp.cp, seed, first + off, n, (float2*)recs);
@@ -850,6 +851,7 @@ int run_siso_tdl_batch_impl(mcle_ctx* ctx, SisoTdlParams pp, int method, uint64_
     if (slice > count) slice = (count + NB - 1) / NB * NB;
     void* recs = nullptr;
     if ((rc = ctx->scratch((size_t)slice * per_real * sizeof(cx<T>), &recs))) return rc;
+    ctx->set_kernel("siso_batched K=%d", pp.K);
     for (uint64_t off = 0; off < count; off += slice) {
         const uint64_t n = count - off < slice ? count - off : slice;
         launch_tdl_symbol_polys<T>(ctx->stream, pp, N + pp.cp, seed, first + off, n, (cx<T>*)recs);
@@ -893,7 +895,8 @@ int run_ofdm_tdl_batched(mcle_ctx* ctx, int dtype, const mcle_ofdm_tdl_cfg* cfg,
     }
     const int W = cfg->fft_size + cfg->cp_size;
     const double xc = 0.5 * (double)(W - 1);
-    const double z = 2.0 * 3.14159265358979323846 * cfg->Fd * pp.dt * (xc + (double)pp.dmax);
+    // (|Fd|: the reference's Jakes generator takes a Doppler of either sign, and the truncation is even in it)
+    const double z = 2.0 * 3.14159265358979323846 * std::fabs(cfg->Fd) * pp.dt * (xc + (double)pp.dmax);
     const double tol = dtype == MCLE_F32 ? 1e-8 : 1e-17;
     int K = 1;
     double term = z * z / 2.0;

@@ -1083,6 +1083,7 @@ int run_tdl_impl(mcle_ctx* ctx, const mcle_ofdm_tdl_cfg* cfg, uint64_t seed, uin
     if (per_cu > 2048 / BLOCK) per_cu = 2048 / BLOCK;
     const uint64_t cap = (uint64_t)ctx->n_cu * per_cu;
     const unsigned grid = (unsigned)(count < cap ? count : cap);
+    ctx->set_kernel("siso_single");
     hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), lds, ctx->stream, pp, mp, seed, first, count, (const cx<T>*)tw,
                        d_counters, d_sym, d_bit);
     MCLE_LAUNCH_CHECK();
@@ -1132,6 +1133,7 @@ int mcle_run_flat_fading(mcle_ctx* ctx, int dtype, const mcle_flat_cfg* cfg, uin
     MCLE_REQUIRE(cfg->noise_var >= 0.0, "noise variance must be non-negative");
     MCLE_REQUIRE(cfg->rayleigh_iid || (cfg->L >= 1 && cfg->L <= kMaxRays), "L must be in [1, %d]", kMaxRays);
     MCLE_REQUIRE(cfg->rayleigh_iid || cfg->Ts > 0.0, "Ts must be positive");
+    MCLE_REQUIRE(cfg->rayleigh_iid || std::isfinite(cfg->Fd), "Fd must be finite");
     MCLE_REQUIRE(count <= 0x7fffffffull, "at most 2^31-1 realizations per call");
     if (count == 0) return MCLE_OK;
     if ((rc = ctx->bind())) return rc;
@@ -1207,6 +1209,7 @@ int mcle_run_mimo_ofdm(mcle_ctx* ctx, int dtype, const mcle_mimo_ofdm_cfg* cfg, 
 
 int mcle_run_ofdm_tdl(mcle_ctx* ctx, int dtype, const mcle_ofdm_tdl_cfg* cfg, uint64_t seed, uint64_t first,
                       uint64_t count, mcle_counters* d_counters, uint32_t* d_sym_err, uint32_t* d_bit_err) {
+    if (ctx) ctx->last_kernel[0] = 0;
     int rc = check_pipe(ctx, dtype, cfg ? cfg->demod_method : 0, cfg);
     if (rc) return rc;
     MCLE_REQUIRE(cfg->cp_size >= 0 && cfg->cp_size <= cfg->fft_size,
@@ -1218,6 +1221,7 @@ int mcle_run_ofdm_tdl(mcle_ctx* ctx, int dtype, const mcle_ofdm_tdl_cfg* cfg, ui
     MCLE_REQUIRE(cfg->L >= 1 && cfg->n_taps * cfg->L <= MCLE_MAX_TAPS * kMaxRays / 4, "too many rays (taps * L <= %d)",
                  MCLE_MAX_TAPS * kMaxRays / 4);
     MCLE_REQUIRE(cfg->Ts > 0.0 && cfg->noise_var >= 0.0, "Ts must be positive and noise_var non-negative");
+    MCLE_REQUIRE(std::isfinite(cfg->Fd), "Fd must be finite (either sign)");
     for (int i = 0; i < cfg->n_taps; ++i) {
         MCLE_REQUIRE(cfg->tap_delay[i] >= 0 && (i == 0 || cfg->tap_delay[i] > cfg->tap_delay[i - 1]),
                      "tap delays must be non-negative and strictly increasing");

@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256) void k_tdl_symbol_polys(SisoTdlParams pp, int 
     const double two_pi = 6.283185307179586476925286766559;
     const double tc = pp.Ts + pp.dt * ((double)((uint64_t)os * W) + xc);
     const Rng rng(seed, first + rl);
-    [[maybe_unused]] const bool small_phase = pp.Fd * (pp.Ts + pp.dt * ((double)(pp.n_ofdm_sym + 1) * W + 256.0)) < 0.25;   // turns, any sample of the run
+    [[maybe_unused]] const bool small_phase = fabs(pp.Fd) * (pp.Ts + pp.dt * ((double)(pp.n_ofdm_sym + 1) * W + 256.0)) < 0.25;   // turns, any sample of the run
     T ar[kTdlMaxK + 1], ai[kTdlMaxK + 1];
 #pragma unroll
     for (int m = 0; m <= kTdlMaxK; ++m) ar[m] = ai[m] = 0;

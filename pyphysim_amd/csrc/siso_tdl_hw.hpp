@@ -388,6 +388,7 @@ int run_siso_tdl_hw(mcle_ctx* ctx, const SisoTdlParams& pp, int method, uint64_t
     const uint64_t floor_n = slice < 64 * NRW ? slice : 64 * NRW;
     if ((rc = ctx->scratch_upto((size_t)slice * one, (size_t)floor_n * one, &recs, &got))) return rc;
     if (got / one < slice) slice = (got / one / NRW) * NRW;
+    ctx->set_kernel("siso_hw K=%d", pp.K);
     for (uint64_t off = 0; off < count; off += slice) {
         const uint64_t n = count - off < slice ? count - off : slice;
         launch_tdl_symbol_polys<T>(ctx->stream, pp, N + pp.cp, seed, first + off, n, (cx<T>*)recs);

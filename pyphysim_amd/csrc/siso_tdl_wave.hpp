@@ -475,6 +475,7 @@ int run_siso_tdl_wave_w(mcle_ctx* ctx, const SisoTdlParams& pp, int method, uint
     const uint64_t floor_n = slice < 64 * NWV ? slice : 64 * NWV;            // scratch_upto: a smaller slice on a crowded device
     if ((rc = ctx->scratch_upto((size_t)slice * one, (size_t)floor_n * one, &recs, &got))) return rc;
     if (got / one < slice) slice = (got / one / NWV) * NWV;
+    ctx->set_kernel("siso_wave N=%d K=%d", N, pp.K);
     for (uint64_t off = 0; off < count; off += slice) {
         const uint64_t n = count - off < slice ? count - off : slice;
         launch_tdl_symbol_polys<T>(ctx->stream, pp, N + pp.cp, seed, first + off, n, (cx<T>*)recs);

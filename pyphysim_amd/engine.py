@@ -124,6 +124,13 @@ class Engine:
         else:
             self.lib.mcle_free(self.ctx, ptr)
 
+    def last_kernel(self):
+        """Diagnostic: the tag of the kernel that served this engine's last config-3 / f1 call (run_ofdm_tdl,
+        run_mimo_ofdm_tdl), e.g. 'siso_wave N=1024 K=6' or 'mimo_coop'; '' before such a call and after a refused one."""
+        buf = ctypes.create_string_buffer(64)
+        check(self.lib.mcle_ctx_last_kernel(self.ctx, buf, 64))
+        return buf.value.decode()
+
     def empty_pool(self):
         """Returns the pooled device buffers and the context's scratch buffer (the record buffers of the two-launch
         pipelines, up to 138-320 MiB) to the allocator."""
