@@ -76,7 +76,29 @@ int mcle_ctx_device_info(mcle_ctx* ctx, int* n_cu, int* lds_bytes, char* name, i
 /* Diagnostic: a short tag naming the kernel that served the context's last mcle_run_ofdm_tdl / mcle_run_mimo_ofdm_tdl call, e.g.
  * "siso_hw K=3", "siso_wave N=1024 K=6", "siso_batched K=9", "siso_mfma", "siso_single", "mimo_wave_parked K=5", "mimo_wave_rt K=3",
  * "mimo_coop" (K: the tap polynomials' order).  Empty before such a call and after one that launched nothing.  Copies at most
- * len - 1 characters and a terminating zero into name. */
+ * len - 1 characters and a terminating zero into name.
+ * The staged operators with more than one form set it too (cleared on entry, so a call that launches nothing leaves it empty):
+ *   mcle_awgn_add / mcle_cmul / mcle_cdiv     "binary pair" (complex64, all three pointers 16-byte aligned), "binary elem"
+ *   mcle_modulate / mcle_demodulate           "modulate pair" / "demodulate pair" (complex64, labels 8- and samples 16-byte
+ *                                             aligned), "modulate elem" / "demodulate elem"
+ *   mcle_randn_c                              "randn_c c64 pair" (complex64, first_sample even, output 16-byte aligned: the
+ *                                             whole pairs as 16-byte stores), "randn_c elem"
+ *   mcle_rand_modulate_batch(_u8)             "rand_modulate pair" (n even, labels 8- and samples 16-byte aligned), "rand_modulate
+ *                                             elem"; "rand_modulate_u8 x16" (n % 16 == 0, both 16-byte aligned), "rand_modulate_u8
+ *                                             elem"
+ *   mcle_blast_encode                         "blast_encode pairs" (nt 2 or 4, even columns, both pointers aligned to a pair of
+ *                                             elements), "blast_encode elem"
+ *   mcle_blast_filter                         "blast_filter staged" (matrix a multiple of 16 bytes, H and G 16-byte aligned,
+ *                                             batch >= 64), "blast_filter direct"
+ *   mcle_blast_decode                         "blast_decode c64 4x4 x4" (16-byte stores: estimates 16-byte aligned),
+ *                                             "blast_decode 4x4", "blast_decode generic"
+ *   mcle_mimo_channel                         "mimo_channel c64 4x4 pair" (even columns, X, Y and noise 16-byte aligned),
+ *                                             "mimo_channel 4x4", "mimo_channel generic"
+ *   mcle_mimo_channel_philox                  "mimo_channel_philox c64 4x4 pair" (as above without the noise array),
+ *                                             "mimo_channel_philox f64 4x4 lane" (even columns), "mimo_channel_philox generic"
+ *   mcle_alamouti_decode                      "alamouti_decode pair" (Y and out aligned to a pair), "alamouti_decode elem"
+ *   mcle_jakes_taps_philox                    "jakes_taps c64 x4" (complex64, even n, taps 16-byte aligned), "jakes_taps elem"
+ * MCLE_OPT_STAGED_GENERIC = 1 selects the last-named (generic) form of each. */
 int mcle_ctx_last_kernel(mcle_ctx* ctx, char* name, int len);
 int mcle_malloc(mcle_ctx* ctx, size_t bytes, void** d_ptr);
 int mcle_free(mcle_ctx* ctx, void* d_ptr);
@@ -170,7 +192,9 @@ enum {
                                       (csrc/walk_f64.hpp: the lane pairs of a chunk of realizations as one index space, decision form
                                       fixed at compile time, records in LDS), 1 = the per-realization walks of rounds 2-5 (A/B and
                                       kernel-vs-kernel tests: identical counters) */
-    MCLE_OPT_COUNT = 16
+    MCLE_OPT_STAGED_GENERIC = 16,  /* 1: every staged operator with more than one form (mcle_ctx_last_kernel lists them) takes its
+                                      generic form whatever the pointers and the shape (A/B and form-vs-form tests) */
+    MCLE_OPT_COUNT = 17
 };
 int mcle_ctx_set_option(mcle_ctx* ctx, int option, long long value);
 int mcle_ctx_get_option(mcle_ctx* ctx, int option, long long* value);
@@ -209,6 +233,12 @@ int mcle_comm_info(mcle_ctx* ctx, int* rank, int* world);
 int mcle_counters_allreduce(mcle_ctx* ctx, mcle_counters* d_counters, int n);
 /* sum of n doubles over the ranks, in place (the 'sum_capacity' style side results of the IA application) */
 int mcle_allreduce_f64(mcle_ctx* ctx, double* d_values, size_t n);
+
+/* ---- pointers of the operators below: any element-aligned device pointer is accepted (8 bytes for complex64, 16 for complex128,
+ *      4 for int32 labels, 1 for byte labels), views into a larger allocation included.  An operator picks its form from the
+ *      pointers and the shape (mcle_ctx_last_kernel names it; MCLE_OPT_STAGED_GENERIC forces the generic one); the values do not
+ *      depend on that choice, bit for bit, except for mcle_mimo_channel_philox in complex64, whose 4x4 pair form adds the noise
+ *      before the products (the other forms after the sum: a rounding-level difference). ------------------------------- */
 
 /* ---- constellation (a1: modulators/fundamental.py:131-146 setConstellation, :396-448 PSK,
  *      :659-777 QAM; the table itself is built by the host mirror) ----------------------- */

@@ -256,8 +256,8 @@ struct mcle_ctx {
 
     // kernel-selection options (mcle_ctx_set_option); 0 = default
     long long opt[MCLE_OPT_COUNT] = {};
-    // which kernel served the last config-3 / f1 call (mcle_ctx_last_kernel; host-only diagnostic): cleared on entry, set where
-    // the chosen kernel launches
+    // which kernel served the last config-3 / f1 call or staged operator with more than one form (mcle_ctx_last_kernel;
+    // host-only diagnostic): cleared on entry, set where the chosen kernel launches
     char last_kernel[48] = {};
     void set_kernel(const char* fmt, ...) {
         va_list ap;
@@ -265,6 +265,13 @@ struct mcle_ctx {
         std::vsnprintf(last_kernel, sizeof(last_kernel), fmt, ap);
         va_end(ap);
     }
+    // the staged operators' form: a literal, no formatting (their timed loops call it once per launch)
+    void set_form(const char* tag) {
+        std::strncpy(last_kernel, tag, sizeof(last_kernel) - 1);
+        last_kernel[sizeof(last_kernel) - 1] = 0;
+    }
+    // the generic form of every staged operator whatever the pointers and the shape (MCLE_OPT_STAGED_GENERIC)
+    bool staged_generic() const { return opt[MCLE_OPT_STAGED_GENERIC] != 0; }
 
     int bind() const;
     int get_twiddles(int n, int dtype, void** d_tw);

@@ -205,7 +205,7 @@ template <typename T>
 __global__ __launch_bounds__(kChBlock) void k_jakes_philox(uint64_t seed, uint64_t first, int L, int S, int sb,
                                                            double Fd, double t0, double dt,
                                                            const double* __restrict__ amp, cx<T>* __restrict__ taps,
-                                                           size_t n) {
+                                                           size_t n, int vec) {
     __shared__ double s_w[kChBlock], s_psi[kChBlock];
     __shared__ float2 s_rot[kChBlock];
     const int s0 = blockIdx.y * sb;
@@ -257,8 +257,9 @@ __global__ __launch_bounds__(kChBlock) void k_jakes_philox(uint64_t seed, uint64
             }
         }
         if constexpr (kRun == 4) {
-            if (i0 + kRun <= n && (n % 2 == 0)) {
-                float4* o4 = reinterpret_cast<float4*>(out + i0);     // rows start 16-byte aligned when n is even
+            if (vec && i0 + kRun <= n) {
+                // vec (host): n even and taps 16-byte aligned, so every row and run starts on a 16-byte boundary
+                float4* o4 = reinterpret_cast<float4*>(out + i0);
                 o4[0] = make_float4(a * re[0], a * im[0], a * re[1], a * im[1]);
                 o4[1] = make_float4(a * re[2], a * im[2], a * re[3], a * im[3]);
                 continue;
@@ -595,6 +596,7 @@ int mcle_tdl_mean_freq_response(mcle_ctx* ctx, int dtype, const void* d_taps, co
 int mcle_jakes_taps_philox(mcle_ctx* ctx, int dtype, uint64_t seed, uint64_t first, uint64_t count, int L,
                            int n_streams, double Fd, double t0, double dt, const double* stream_amp, void* d_taps,
                            size_t n_samples) {
+    if (ctx) ctx->last_kernel[0] = 0;
     MCLE_REQUIRE(ctx != nullptr && stream_amp != nullptr, "null argument");
     MCLE_REQUIRE(dtype == MCLE_F32 || dtype == MCLE_F64, "dtype must be MCLE_F32 or MCLE_F64");
     MCLE_REQUIRE(L >= 1 && L <= 64, "L must be in [1, 64]");
@@ -617,12 +619,15 @@ int mcle_jakes_taps_philox(mcle_ctx* ctx, int dtype, uint64_t seed, uint64_t fir
     if (sb > 16) sb = 16;
     if (sb > n_streams) sb = n_streams;
     dim3 grid(1u, (unsigned)((n_streams + sb - 1) / sb), (unsigned)count);
+    // complex64 runs of four samples as two 16-byte stores: even rows on a 16-byte aligned base
+    const int vec = dtype == MCLE_F32 && !ctx->staged_generic() && n_samples % 2 == 0 && ((uintptr_t)d_taps & 15u) == 0;
     if (dtype == MCLE_F32)
         hipLaunchKernelGGL(k_jakes_philox<float>, grid, dim3(kChBlock), 0, ctx->stream, seed, first, L, n_streams, sb,
-                           Fd, t0, dt, (const double*)d_amp, (float2*)d_taps, n_samples);
+                           Fd, t0, dt, (const double*)d_amp, (float2*)d_taps, n_samples, vec);
     else
         hipLaunchKernelGGL(k_jakes_philox<double>, grid, dim3(kChBlock), 0, ctx->stream, seed, first, L, n_streams,
-                           sb, Fd, t0, dt, (const double*)d_amp, (double2*)d_taps, n_samples);
+                           sb, Fd, t0, dt, (const double*)d_amp, (double2*)d_taps, n_samples, 0);
+    ctx->set_form(vec ? "jakes_taps c64 x4" : "jakes_taps elem");
     MCLE_LAUNCH_CHECK();
     return MCLE_OK;
 }

@@ -134,10 +134,11 @@ __global__ __launch_bounds__(64) void k_blast_filter_staged(const cx<T>* __restr
     }
 }
 
-// est[b][c*nt + a] = sum_r G[b][a][r] Y[b][r][c]
+// est[b][c*nt + a] = sum_r G[b][a][r] Y[b][r][c].  form (host): 0 = the generic loop, 1 = 4x4 (a column's four Y in registers),
+// 2 = the same with 16-byte stores (complex64, est 16-byte aligned); all three keep one association.
 template <typename T>
 __global__ __launch_bounds__(kMimoBlock) void k_blast_decode(const cx<T>* __restrict__ G, const cx<T>* __restrict__ Y,
-                                                             int nr, int nt, size_t ns, cx<T>* __restrict__ est) {
+                                                             int nr, int nt, size_t ns, cx<T>* __restrict__ est, int form) {
     const size_t b = blockIdx.y;
     const cx<T>* Gb = G + b * (size_t)nt * nr;
     const cx<T>* Yb = Y + b * (size_t)nr * ns;
@@ -145,7 +146,7 @@ __global__ __launch_bounds__(kMimoBlock) void k_blast_decode(const cx<T>* __rest
     // one thread per column; the nt interleaved results of a column are contiguous in memory and leave as
     // 16-byte stores (four strided 8-byte streams per wave were the bottleneck of the first version)
     for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < ns; c += (size_t)gridDim.x * blockDim.x) {
-        if (nt == 4 && nr == 4) {
+        if (form > 0) {
             cx<T> y[4], e[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) y[r] = Yb[(size_t)r * ns + c];
@@ -157,13 +158,15 @@ __global__ __launch_bounds__(kMimoBlock) void k_blast_decode(const cx<T>* __rest
                 e[a] = acc;
             }
             if constexpr (sizeof(T) == 4) {
-                float4* o4 = reinterpret_cast<float4*>(eb + c * 4);
-                o4[0] = make_float4(e[0].x, e[0].y, e[1].x, e[1].y);
-                o4[1] = make_float4(e[2].x, e[2].y, e[3].x, e[3].y);
-            } else {
-#pragma unroll
-                for (int a = 0; a < 4; ++a) eb[c * 4 + a] = e[a];
+                if (form == 2) {
+                    float4* o4 = reinterpret_cast<float4*>(eb + c * 4);
+                    o4[0] = make_float4(e[0].x, e[0].y, e[1].x, e[1].y);
+                    o4[1] = make_float4(e[2].x, e[2].y, e[3].x, e[3].y);
+                    continue;
+                }
             }
+#pragma unroll
+            for (int a = 0; a < 4; ++a) eb[c * 4 + a] = e[a];
         } else {
             for (int a = 0; a < nt; ++a) {
                 cx<T> acc = mk<T>(0, 0);
@@ -194,16 +197,17 @@ __global__ __launch_bounds__(kMimoBlock) void k_blast_decode_persc(const cx<T>* 
     }
 }
 
-// Y[b][r][c] = sum_a H[b][r][a] X[b][a][c] (+ sigma * noise[b][r][c])
+// Y[b][r][c] = sum_a H[b][r][a] X[b][a][c] (+ sigma * noise[b][r][c]).  form (host): 0 = the generic loop, 1 = 4x4 with H in
+// registers, 2 = 4x4 complex64 pairs (even ns, 16-byte aligned rows); one association (cfma order, noise after the sum).
 template <typename T>
 __global__ __launch_bounds__(kMimoBlock) void k_mimo_channel(const cx<T>* __restrict__ H, const cx<T>* __restrict__ X,
                                                              const cx<T>* __restrict__ nz, T sigma, int nr, int nt,
-                                                             size_t ns, cx<T>* __restrict__ Y, int vec) {
+                                                             size_t ns, cx<T>* __restrict__ Y, int form) {
     const size_t b = blockIdx.y;
     const cx<T>* Hb = H + b * (size_t)nr * nt;
     const cx<T>* Xb = X + b * (size_t)nt * ns;
     if constexpr (sizeof(T) == 4) {
-        if (vec) {   // 4x4, even ns, 16-byte aligned rows: two columns per thread, every stream in 16-byte accesses
+        if (form == 2) {   // 4x4, even ns, 16-byte aligned rows: two columns per thread, every stream in 16-byte accesses
             float2 Hr[4][4];
 #pragma unroll
             for (int r = 0; r < 4; ++r)
@@ -235,7 +239,7 @@ __global__ __launch_bounds__(kMimoBlock) void k_mimo_channel(const cx<T>* __rest
             return;
         }
     }
-    if (nr == 4 && nt == 4) {   // H in registers, every column of X read once (the loop below reads it once per output row)
+    if (form == 1) {   // 4x4: H in registers, every column of X read once (the loop below reads it once per output row)
         cx<T> Hr[4][4];
 #pragma unroll
         for (int r = 0; r < 4; ++r)
@@ -360,7 +364,10 @@ __global__ __launch_bounds__(kMimoBlock) void k_mimo_channel_philox(const cx<T>*
                 }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const double2 z = cn_from_words_lds(w[r][0], w[r][1], sigma, s_bm);
+                    double2 z = cn_from_words_lds(w[r][0], w[r][1], sigma, s_bm);
+                    // the noise rounded before the add, as in the generic loop (there it reaches the add through a branch;
+                    // here the multiply rad * cos would otherwise contract into it: one rounding less, different bits)
+                    asm volatile("" : "+v"(z.x), "+v"(z.y));
                     double2 s0 = mk<double>(0, 0);
 #pragma unroll
                     for (int a = 0; a < 4; ++a) s0 = cfma(Hr[r][a], x[a], s0);
@@ -555,15 +562,17 @@ __global__ __launch_bounds__(64) void k_gmd_filters(const cx<T>* __restrict__ Hg
 template <typename T, int NT, int NR>
 int launch_filter(mcle_ctx* ctx, const void* d_H, double nv, void* d_G, uint32_t* d_skipped, size_t batch) {
     if constexpr ((NT * NR * sizeof(cx<T>)) % 16 == 0) {
-        if ((((uintptr_t)d_H | (uintptr_t)d_G) & 15) == 0 && batch >= 64) {
+        if (!ctx->staged_generic() && (((uintptr_t)d_H | (uintptr_t)d_G) & 15) == 0 && batch >= 64) {
             hipLaunchKernelGGL((k_blast_filter_staged<T, NT, NR>), dim3(grid_for(ctx, batch, 64, 16)), dim3(64), 0,
                                ctx->stream, (const cx<T>*)d_H, nv, (cx<T>*)d_G, d_skipped, batch);
+            ctx->set_form("blast_filter staged");
             MCLE_LAUNCH_CHECK();
             return MCLE_OK;
         }
     }
     hipLaunchKernelGGL((k_blast_filter<T, NT, NR>), dim3(grid_for(ctx, batch, 64, 16)), dim3(64), 0, ctx->stream,
                        (const cx<T>*)d_H, nv, (cx<T>*)d_G, d_skipped, batch);
+    ctx->set_form("blast_filter direct");
     MCLE_LAUNCH_CHECK();
     return MCLE_OK;
 }
@@ -628,6 +637,7 @@ using namespace mcle;
 extern "C" {
 
 int mcle_blast_encode(mcle_ctx* ctx, int dtype, const void* d_x, int nt, size_t n, void* d_X, size_t batch) {
+    if (ctx) ctx->last_kernel[0] = 0;
     int rc = check_mimo(ctx, dtype, 1, nt, batch);
     if (rc) return rc;
     // mimo.py:633-637
@@ -638,7 +648,8 @@ int mcle_blast_encode(mcle_ctx* ctx, int dtype, const void* d_x, int nt, size_t 
     dim3 grid((unsigned)grid_for(ctx, n, kMimoBlock, 4), (unsigned)batch);
     const double s = 1.0 / std::sqrt((double)nt);
     const size_t ns_ = n / nt, pair_bytes = dtype == MCLE_F32 ? 16 : 32;
-    if ((nt == 2 || nt == 4) && ns_ % 2 == 0 && ((uintptr_t)d_x % pair_bytes) == 0 && ((uintptr_t)d_X % pair_bytes) == 0) {
+    if (!ctx->staged_generic() && (nt == 2 || nt == 4) && ns_ % 2 == 0 && ((uintptr_t)d_x % pair_bytes) == 0 &&
+        ((uintptr_t)d_X % pair_bytes) == 0) {
         dim3 gridp((unsigned)grid_for(ctx, ns_ / 2, kMimoBlock, 4), (unsigned)batch);
         if (dtype == MCLE_F32 && nt == 2)
             hipLaunchKernelGGL((k_blast_encode_pairs<float, 2>), gridp, dim3(kMimoBlock), 0, ctx->stream, (const float2*)d_x,
@@ -652,6 +663,7 @@ int mcle_blast_encode(mcle_ctx* ctx, int dtype, const void* d_x, int nt, size_t 
         else
             hipLaunchKernelGGL((k_blast_encode_pairs<double, 4>), gridp, dim3(kMimoBlock), 0, ctx->stream,
                                (const double2*)d_x, ns_, s, (double2*)d_X);
+        ctx->set_form("blast_encode pairs");
         MCLE_LAUNCH_CHECK();
         return MCLE_OK;
     }
@@ -661,12 +673,14 @@ int mcle_blast_encode(mcle_ctx* ctx, int dtype, const void* d_x, int nt, size_t 
     else
         hipLaunchKernelGGL(k_blast_encode<double>, grid, dim3(kMimoBlock), 0, ctx->stream, (const double2*)d_x, nt,
                            n / nt, s, (double2*)d_X);
+    ctx->set_form("blast_encode elem");
     MCLE_LAUNCH_CHECK();
     return MCLE_OK;
 }
 
 int mcle_blast_filter(mcle_ctx* ctx, int dtype, const void* d_H, int nr, int nt, double noise_var, void* d_G,
                       uint32_t* d_skipped, size_t batch) {
+    if (ctx) ctx->last_kernel[0] = 0;
     MCLE_REQUIRE(ctx != nullptr, "null context");
     MCLE_REQUIRE(dtype == MCLE_F32 || dtype == MCLE_F64, "dtype must be MCLE_F32 or MCLE_F64");
     // mimo.py:553
@@ -681,45 +695,56 @@ int mcle_blast_filter(mcle_ctx* ctx, int dtype, const void* d_H, int nr, int nt,
 
 int mcle_blast_decode(mcle_ctx* ctx, int dtype, const void* d_G, const void* d_Y, int nr, int nt, size_t ns,
                       void* d_est, size_t batch) {
+    if (ctx) ctx->last_kernel[0] = 0;
     int rc = check_mimo(ctx, dtype, nr, nt, batch);
     if (rc) return rc;
     if (ns == 0 || batch == 0) return MCLE_OK;
     if ((rc = ctx->bind())) return rc;
     dim3 grid((unsigned)grid_for(ctx, ns, kMimoBlock, 4), (unsigned)batch);
+    // complex64 4x4: a column's four estimates leave as two 16-byte stores when est is 16-byte aligned (every batch item's
+    // and column's run of estimates then starts on a 32-byte step from it)
+    const bool four = nr == 4 && nt == 4 && !ctx->staged_generic();
+    const int form = !four ? 0 : (dtype == MCLE_F32 && ((uintptr_t)d_est & 15u) == 0) ? 2 : 1;
     if (dtype == MCLE_F32)
         hipLaunchKernelGGL(k_blast_decode<float>, grid, dim3(kMimoBlock), 0, ctx->stream, (const float2*)d_G,
-                           (const float2*)d_Y, nr, nt, ns, (float2*)d_est);
+                           (const float2*)d_Y, nr, nt, ns, (float2*)d_est, form);
     else
         hipLaunchKernelGGL(k_blast_decode<double>, grid, dim3(kMimoBlock), 0, ctx->stream, (const double2*)d_G,
-                           (const double2*)d_Y, nr, nt, ns, (double2*)d_est);
+                           (const double2*)d_Y, nr, nt, ns, (double2*)d_est, form);
+    ctx->set_form(form == 2 ? "blast_decode c64 4x4 x4" : form == 1 ? "blast_decode 4x4" : "blast_decode generic");
     MCLE_LAUNCH_CHECK();
     return MCLE_OK;
 }
 
 int mcle_mimo_channel(mcle_ctx* ctx, int dtype, const void* d_H, const void* d_X, const void* d_noise,
                       double noise_var, int nr, int nt, size_t ns, void* d_Y, size_t batch) {
+    if (ctx) ctx->last_kernel[0] = 0;
     int rc = check_mimo(ctx, dtype, nr, nt, batch);
     if (rc) return rc;
     MCLE_REQUIRE(noise_var >= 0.0, "noise variance must be non-negative");
     if (ns == 0 || batch == 0) return MCLE_OK;
     if ((rc = ctx->bind())) return rc;
-    const int vec = nr == 4 && nt == 4 && ns % 2 == 0 &&
+    const bool four = nr == 4 && nt == 4 && !ctx->staged_generic();
+    const int vec = four && dtype == MCLE_F32 && ns % 2 == 0 &&
                     ((((uintptr_t)d_X) | ((uintptr_t)d_Y) | ((uintptr_t)d_noise)) & 15u) == 0;
+    const int form = vec ? 2 : four ? 1 : 0;
     dim3 grid((unsigned)grid_for(ctx, vec ? ns / 2 : ns, kMimoBlock, 4), (unsigned)batch);
     if (dtype == MCLE_F32)
         hipLaunchKernelGGL(k_mimo_channel<float>, grid, dim3(kMimoBlock), 0, ctx->stream, (const float2*)d_H,
                            (const float2*)d_X, (const float2*)d_noise, (float)std::sqrt(noise_var), nr, nt, ns,
-                           (float2*)d_Y, vec);
+                           (float2*)d_Y, form);
     else
         hipLaunchKernelGGL(k_mimo_channel<double>, grid, dim3(kMimoBlock), 0, ctx->stream, (const double2*)d_H,
                            (const double2*)d_X, (const double2*)d_noise, std::sqrt(noise_var), nr, nt, ns,
-                           (double2*)d_Y, 0);
+                           (double2*)d_Y, form);
+    ctx->set_form(form == 2 ? "mimo_channel c64 4x4 pair" : form == 1 ? "mimo_channel 4x4" : "mimo_channel generic");
     MCLE_LAUNCH_CHECK();
     return MCLE_OK;
 }
 
 int mcle_mimo_channel_philox(mcle_ctx* ctx, int dtype, const void* d_H, const void* d_X, uint64_t seed, uint64_t first,
                              double noise_var, int nr, int nt, size_t ns, void* d_Y, size_t batch) {
+    if (ctx) ctx->last_kernel[0] = 0;
     int rc = check_mimo(ctx, dtype, nr, nt, batch);
     if (rc) return rc;
     MCLE_REQUIRE(noise_var >= 0.0, "noise variance must be non-negative");
@@ -727,7 +752,9 @@ int mcle_mimo_channel_philox(mcle_ctx* ctx, int dtype, const void* d_H, const vo
     MCLE_REQUIRE((uint64_t)nr * ns < (1ull << 33), "more than 2^33 noise samples per realization");
     if (ns == 0 || batch == 0) return MCLE_OK;
     if ((rc = ctx->bind())) return rc;
-    const int vec = dtype == MCLE_F32 && nr == 4 && nt == 4 && ns % 2 == 0 &&
+    // complex64: 16-byte accesses (the kernel keys them on sizeof(T)); complex128: the lane-exchange form, whose element-aligned
+    // pointers always pass the alignment term
+    const int vec = !ctx->staged_generic() && nr == 4 && nt == 4 && ns % 2 == 0 &&
                     ((((uintptr_t)d_X) | ((uintptr_t)d_Y)) & 15u) == 0;
     // (complex128 4 x 4: one column per lane; everything else two)
     dim3 grid((unsigned)grid_for(ctx, (dtype == MCLE_F64 && vec) ? ns : (ns + 1) / 2, kMimoBlock, 4), (unsigned)batch);
@@ -737,6 +764,8 @@ int mcle_mimo_channel_philox(mcle_ctx* ctx, int dtype, const void* d_H, const vo
     else
         hipLaunchKernelGGL(k_mimo_channel_philox<double>, grid, dim3(kMimoBlock), 0, ctx->stream, (const double2*)d_H,
                            (const double2*)d_X, seed, first, std::sqrt(noise_var), nr, nt, ns, (double2*)d_Y, vec);
+    ctx->set_form(!vec ? "mimo_channel_philox generic" : dtype == MCLE_F32 ? "mimo_channel_philox c64 4x4 pair"
+                                                                           : "mimo_channel_philox f64 4x4 lane");
     MCLE_LAUNCH_CHECK();
     return MCLE_OK;
 }
@@ -761,6 +790,7 @@ int mcle_alamouti_encode(mcle_ctx* ctx, int dtype, const void* d_x, size_t n, vo
 
 int mcle_alamouti_decode(mcle_ctx* ctx, int dtype, const void* d_H, const void* d_Y, int nr, size_t n, void* d_out,
                          size_t batch) {
+    if (ctx) ctx->last_kernel[0] = 0;
     int rc = check_mimo(ctx, dtype, nr, 2, batch);
     if (rc) return rc;
     MCLE_REQUIRE(n % 2 == 0, "Alamouti needs an even number of symbols");
@@ -768,13 +798,14 @@ int mcle_alamouti_decode(mcle_ctx* ctx, int dtype, const void* d_H, const void* 
     if ((rc = ctx->bind())) return rc;
     dim3 grid((unsigned)grid_for(ctx, n / 2, kMimoBlock, 4), (unsigned)batch);
     const size_t pair = dtype == MCLE_F32 ? 16 : 32;
-    const bool vec = ((uintptr_t)d_Y % pair) == 0 && ((uintptr_t)d_out % pair) == 0;
+    const bool vec = !ctx->staged_generic() && ((uintptr_t)d_Y % pair) == 0 && ((uintptr_t)d_out % pair) == 0;
     if (dtype == MCLE_F32)
         hipLaunchKernelGGL(k_alamouti_decode<float>, grid, dim3(kMimoBlock), 0, ctx->stream, (const float2*)d_H,
                            (const float2*)d_Y, nr, n, (float)std::sqrt(2.0), (float2*)d_out, vec);
     else
         hipLaunchKernelGGL(k_alamouti_decode<double>, grid, dim3(kMimoBlock), 0, ctx->stream, (const double2*)d_H,
                            (const double2*)d_Y, nr, n, std::sqrt(2.0), (double2*)d_out, vec);
+    ctx->set_form(vec ? "alamouti_decode pair" : "alamouti_decode elem");
     MCLE_LAUNCH_CHECK();
     return MCLE_OK;
 }

@@ -228,7 +228,8 @@ __global__ __launch_bounds__(kBlock) void k_binary(const cx<T>* __restrict__ x, 
 
 template <typename Op>
 int launch_binary(mcle_ctx* ctx, int dtype, const void* d_a, const void* d_b, double param, void* d_out, size_t n) {
-    const int vec = ((((uintptr_t)d_a) | ((uintptr_t)d_b) | ((uintptr_t)d_out)) & 15u) == 0;
+    const int vec = dtype == MCLE_F32 && !ctx->staged_generic() &&
+                    ((((uintptr_t)d_a) | ((uintptr_t)d_b) | ((uintptr_t)d_out)) & 15u) == 0;
     const int grid = grid_for(ctx, dtype == MCLE_F32 && vec ? (n + 1) / 2 : n, kBlock);
     if (dtype == MCLE_F32)
         hipLaunchKernelGGL((k_binary<float, Op>), dim3(grid), dim3(kBlock), 0, ctx->stream, (const float2*)d_a,
@@ -236,6 +237,7 @@ int launch_binary(mcle_ctx* ctx, int dtype, const void* d_a, const void* d_b, do
     else
         hipLaunchKernelGGL((k_binary<double, Op>), dim3(grid), dim3(kBlock), 0, ctx->stream, (const double2*)d_a,
                            (const double2*)d_b, param, (double2*)d_out, n, 0);
+    ctx->set_form(vec ? "binary pair" : "binary elem");
     MCLE_LAUNCH_CHECK();
     return MCLE_OK;
 }
@@ -243,11 +245,11 @@ int launch_binary(mcle_ctx* ctx, int dtype, const void* d_a, const void* d_b, do
 // One thread per Philox block, every word used: block b of the stream holds the complex normals 2b and 2b + 1
 // (philox.hpp), so a thread owns the pair and writes it as one 16-byte store where both fall inside [first, first + n)
 // and the output is aligned (a sample-per-thread form evaluated every block twice).
+// `vec` (host check): complex64, `first` even and `out` 16-byte aligned.
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_randn_c(Rng rng, uint32_t stream, uint64_t first, T sigma,
-                                                    cx<T>* __restrict__ out, size_t n) {
+                                                    cx<T>* __restrict__ out, size_t n, int vec) {
     const uint64_t b_lo = first >> 1, b_hi = (first + n - 1) >> 1;          // blocks touched
-    const bool vec = sizeof(T) == 4 && ((first & 1) == 0) && (((uintptr_t)out & 15) == 0);
     for (uint64_t b = b_lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; b <= b_hi;
          b += (uint64_t)gridDim.x * blockDim.x) {
         cx<T> z0, z1;
@@ -422,6 +424,7 @@ using namespace mcle;
 extern "C" {
 
 int mcle_modulate(mcle_ctx* ctx, int dtype, const int32_t* d_idx, void* d_out, size_t n) {
+    if (ctx) ctx->last_kernel[0] = 0;
     int rc = check_modem(ctx, dtype, MCLE_DEMOD_MINDIST);
     if (rc) return rc;
     MCLE_REQUIRE(ctx->M <= kMaxM, "constellation too large for the LDS table (%d > %d)", ctx->M, kMaxM);
@@ -430,7 +433,7 @@ int mcle_modulate(mcle_ctx* ctx, int dtype, const int32_t* d_idx, void* d_out, s
     void* st = nullptr;
     if ((rc = ctx->scratch(sizeof(unsigned), &st))) return rc;
     MCLE_HIP(hipMemsetAsync(st, 0, sizeof(unsigned), ctx->stream));
-    const int vec = dtype == MCLE_F32 && (((uintptr_t)d_idx & 7u) | ((uintptr_t)d_out & 15u)) == 0;
+    const int vec = dtype == MCLE_F32 && !ctx->staged_generic() && (((uintptr_t)d_idx & 7u) | ((uintptr_t)d_out & 15u)) == 0;
     const int grid = grid_for(ctx, vec ? (n + 1) / 2 : n, kBlock);
     if (dtype == MCLE_F32)
         hipLaunchKernelGGL(k_modulate<float>, dim3(grid), dim3(kBlock), 0, ctx->stream, modem_params<float>(ctx, 0),
@@ -438,6 +441,7 @@ int mcle_modulate(mcle_ctx* ctx, int dtype, const int32_t* d_idx, void* d_out, s
     else
         hipLaunchKernelGGL(k_modulate<double>, dim3(grid), dim3(kBlock), 0, ctx->stream, modem_params<double>(ctx, 0),
                            d_idx, (double2*)d_out, n, (unsigned*)st, 0);
+    ctx->set_form(vec ? "modulate pair" : "modulate elem");
     MCLE_LAUNCH_CHECK();
     unsigned flag = 0;
     MCLE_HIP(hipMemcpyAsync(&flag, st, sizeof(flag), hipMemcpyDeviceToHost, ctx->stream));
@@ -448,11 +452,12 @@ int mcle_modulate(mcle_ctx* ctx, int dtype, const int32_t* d_idx, void* d_out, s
 }
 
 int mcle_demodulate(mcle_ctx* ctx, int dtype, int method, const void* d_rx, int32_t* d_idx, size_t n) {
+    if (ctx) ctx->last_kernel[0] = 0;
     int rc = check_modem(ctx, dtype, method);
     if (rc) return rc;
     if (n == 0) return MCLE_OK;
     if ((rc = ctx->bind())) return rc;
-    const int vec = dtype == MCLE_F32 && (((uintptr_t)d_rx & 15u) | ((uintptr_t)d_idx & 7u)) == 0;
+    const int vec = dtype == MCLE_F32 && !ctx->staged_generic() && (((uintptr_t)d_rx & 15u) | ((uintptr_t)d_idx & 7u)) == 0;
     const int grid = grid_for(ctx, vec ? (n + 1) / 2 : n, kBlock);
     if (dtype == MCLE_F32)
         hipLaunchKernelGGL(k_demodulate<float>, dim3(grid), dim3(kBlock), 0, ctx->stream,
@@ -460,6 +465,7 @@ int mcle_demodulate(mcle_ctx* ctx, int dtype, int method, const void* d_rx, int3
     else
         hipLaunchKernelGGL(k_demodulate<double>, dim3(grid), dim3(kBlock), 0, ctx->stream,
                            modem_params<double>(ctx, method), (const double2*)d_rx, d_idx, n, 0);
+    ctx->set_form(vec ? "demodulate pair" : "demodulate elem");
     MCLE_LAUNCH_CHECK();
     return MCLE_OK;
 }
@@ -521,6 +527,7 @@ int mcle_demod_count_u8(mcle_ctx* ctx, int dtype, int method, const void* d_rx, 
 
 int mcle_randn_c(mcle_ctx* ctx, int dtype, uint64_t seed, uint64_t realization, uint32_t stream,
                  uint64_t first_sample, double variance, void* d_out, size_t n) {
+    if (ctx) ctx->last_kernel[0] = 0;
     MCLE_REQUIRE(ctx != nullptr, "null context");
     MCLE_REQUIRE(dtype == MCLE_F32 || dtype == MCLE_F64, "dtype must be MCLE_F32 or MCLE_F64");
     MCLE_REQUIRE(variance >= 0.0, "variance must be non-negative");
@@ -529,12 +536,14 @@ int mcle_randn_c(mcle_ctx* ctx, int dtype, uint64_t seed, uint64_t realization, 
     if (rc) return rc;
     Rng rng(seed, realization);
     const int grid = grid_for(ctx, n / 2 + 1, kBlock);
+    const int vec = dtype == MCLE_F32 && !ctx->staged_generic() && (first_sample & 1) == 0 && ((uintptr_t)d_out & 15u) == 0;
     if (dtype == MCLE_F32)
         hipLaunchKernelGGL(k_randn_c<float>, dim3(grid), dim3(kBlock), 0, ctx->stream, rng, stream, first_sample,
-                           (float)sqrt(variance), (float2*)d_out, n);
+                           (float)sqrt(variance), (float2*)d_out, n, vec);
     else
         hipLaunchKernelGGL(k_randn_c<double>, dim3(grid), dim3(kBlock), 0, ctx->stream, rng, stream, first_sample,
-                           sqrt(variance), (double2*)d_out, n);
+                           sqrt(variance), (double2*)d_out, n, 0);
+    ctx->set_form(vec ? "randn_c c64 pair" : "randn_c elem");
     MCLE_LAUNCH_CHECK();
     return MCLE_OK;
 }
@@ -569,6 +578,7 @@ int mcle_rand_symbols_batch(mcle_ctx* ctx, uint64_t seed, uint64_t first_realiza
 
 int mcle_rand_modulate_batch(mcle_ctx* ctx, int dtype, uint64_t seed, uint64_t first_realization, uint64_t count,
                              int32_t* d_idx, void* d_sym, size_t n) {
+    if (ctx) ctx->last_kernel[0] = 0;
     int rc = check_modem(ctx, dtype, MCLE_DEMOD_MINDIST);
     if (rc) return rc;
     MCLE_REQUIRE((ctx->M & (ctx->M - 1)) == 0 && ctx->M >= 2 && ctx->M <= 256,
@@ -579,7 +589,7 @@ int mcle_rand_modulate_batch(mcle_ctx* ctx, int dtype, uint64_t seed, uint64_t f
     if (n == 0 || count == 0) return MCLE_OK;
     if ((rc = ctx->bind())) return rc;
     dim3 grid((unsigned)grid_for(ctx, n / 16 + 1, kBlock, 2), (unsigned)count);
-    const int vec_ok = (n & 1) == 0 && ((uintptr_t)d_idx & 7u) == 0 && ((uintptr_t)d_sym & 15u) == 0;
+    const int vec_ok = !ctx->staged_generic() && (n & 1) == 0 && ((uintptr_t)d_idx & 7u) == 0 && ((uintptr_t)d_sym & 15u) == 0;
     if (dtype == MCLE_F32)
         hipLaunchKernelGGL(k_rand_modulate_batch<float>, grid, dim3(kBlock), 0, ctx->stream,
                            modem_params<float>(ctx, MCLE_DEMOD_MINDIST), seed, first_realization, (uint32_t)(ctx->M - 1),
@@ -588,12 +598,14 @@ int mcle_rand_modulate_batch(mcle_ctx* ctx, int dtype, uint64_t seed, uint64_t f
         hipLaunchKernelGGL(k_rand_modulate_batch<double>, grid, dim3(kBlock), 0, ctx->stream,
                            modem_params<double>(ctx, MCLE_DEMOD_MINDIST), seed, first_realization, (uint32_t)(ctx->M - 1),
                            d_idx, (double2*)d_sym, n, vec_ok);
+    ctx->set_form(vec_ok ? "rand_modulate pair" : "rand_modulate elem");
     MCLE_LAUNCH_CHECK();
     return MCLE_OK;
 }
 
 int mcle_rand_modulate_batch_u8(mcle_ctx* ctx, int dtype, uint64_t seed, uint64_t first_realization, uint64_t count,
                                 uint8_t* d_idx, void* d_sym, size_t n) {
+    if (ctx) ctx->last_kernel[0] = 0;
     int rc = check_modem(ctx, dtype, MCLE_DEMOD_MINDIST);
     if (rc) return rc;
     MCLE_REQUIRE((ctx->M & (ctx->M - 1)) == 0 && ctx->M >= 2 && ctx->M <= 256,
@@ -604,7 +616,7 @@ int mcle_rand_modulate_batch_u8(mcle_ctx* ctx, int dtype, uint64_t seed, uint64_
     if ((rc = ctx->bind())) return rc;
     dim3 grid((unsigned)grid_for(ctx, n / 16 + 1, kBlock, 2), (unsigned)count);
     // vector stores: rows of whole 16-label groups on 16-byte boundaries (labels and samples)
-    const int vec_ok = (n & 15) == 0 && ((uintptr_t)d_idx & 15u) == 0 && ((uintptr_t)d_sym & 15u) == 0;
+    const int vec_ok = !ctx->staged_generic() && (n & 15) == 0 && ((uintptr_t)d_idx & 15u) == 0 && ((uintptr_t)d_sym & 15u) == 0;
     if (dtype == MCLE_F32)
         hipLaunchKernelGGL((k_rand_modulate_batch<float, uint8_t>), grid, dim3(kBlock), 0, ctx->stream,
                            modem_params<float>(ctx, MCLE_DEMOD_MINDIST), seed, first_realization, (uint32_t)(ctx->M - 1),
@@ -613,12 +625,14 @@ int mcle_rand_modulate_batch_u8(mcle_ctx* ctx, int dtype, uint64_t seed, uint64_
         hipLaunchKernelGGL((k_rand_modulate_batch<double, uint8_t>), grid, dim3(kBlock), 0, ctx->stream,
                            modem_params<double>(ctx, MCLE_DEMOD_MINDIST), seed, first_realization, (uint32_t)(ctx->M - 1),
                            d_idx, (double2*)d_sym, n, vec_ok);
+    ctx->set_form(vec_ok ? "rand_modulate_u8 x16" : "rand_modulate_u8 elem");
     MCLE_LAUNCH_CHECK();
     return MCLE_OK;
 }
 
 int mcle_awgn_add(mcle_ctx* ctx, int dtype, const void* d_x, const void* d_noise, double noise_var, void* d_y,
                   size_t n) {
+    if (ctx) ctx->last_kernel[0] = 0;
     MCLE_REQUIRE(ctx != nullptr, "null context");
     MCLE_REQUIRE(dtype == MCLE_F32 || dtype == MCLE_F64, "dtype must be MCLE_F32 or MCLE_F64");
     MCLE_REQUIRE(noise_var >= 0.0, "noise variance must be non-negative");
@@ -629,6 +643,7 @@ int mcle_awgn_add(mcle_ctx* ctx, int dtype, const void* d_x, const void* d_noise
 }
 
 int mcle_cmul(mcle_ctx* ctx, int dtype, const void* d_a, const void* d_b, void* d_out, size_t n) {
+    if (ctx) ctx->last_kernel[0] = 0;
     MCLE_REQUIRE(ctx != nullptr, "null context");
     MCLE_REQUIRE(dtype == MCLE_F32 || dtype == MCLE_F64, "dtype must be MCLE_F32 or MCLE_F64");
     if (n == 0) return MCLE_OK;
@@ -638,6 +653,7 @@ int mcle_cmul(mcle_ctx* ctx, int dtype, const void* d_a, const void* d_b, void* 
 }
 
 int mcle_cdiv(mcle_ctx* ctx, int dtype, const void* d_num, const void* d_den, void* d_out, size_t n) {
+    if (ctx) ctx->last_kernel[0] = 0;
     MCLE_REQUIRE(ctx != nullptr, "null context");
     MCLE_REQUIRE(dtype == MCLE_F32 || dtype == MCLE_F64, "dtype must be MCLE_F32 or MCLE_F64");
     if (n == 0) return MCLE_OK;
