@@ -147,7 +147,12 @@ enum {
                                       eighth-wave kernel (512 threads).  (1024, 4x4): since the end of round 6 the DEFAULT (0) is the
                                       quarter-wave decomposition with the decode on the matrix cores as well (pipeline_mimo_pw.hip,
                                       NW = 4; 263 = the same, explicit; 264 = two wavefronts per SIMD); 260 / 262 select the first
-                                      quarter-wave kernel (pipeline_mimo_qw.hip, VALU decode) */
+                                      quarter-wave kernel (pipeline_mimo_qw.hip, VALU decode).
+                                      Since round 7 the part-wave kernel (512, 1024 and 2048 points) adds the signal AFTER the
+                                      receive transform -- the channel is flat, so only the noise is transformed and H X joins it
+                                      on v_mfma_f64_4x4x4 in front of the decode; 265 = its time-domain form of round 6 (transmit
+                                      transform, channel on the samples) at all three sizes, same counts: the A/B partner.
+                                      mcle_ctx_last_kernel names the size and the form: "mimo_ofdm_pw<NW>/freq" or ".../time". */
     MCLE_OPT_BD_RUNTIME_SOLVE = 9, /* 1: the block-diagonalisation pipeline solves with the run-time-sized routine (private
                                       arrays in scratch) also where the compile-time-sized one (K nr <= 6) applies */
     MCLE_OPT_DEMOD_NOCERT = 10,    /* 1: min-distance decisions of a square Gray QAM always through the table search (candidate

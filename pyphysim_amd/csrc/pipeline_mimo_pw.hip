@@ -24,6 +24,9 @@
 // LDS: NW planes of 8.5 KiB + tables -> 512: 27 KiB (five workgroups per CU fit, three wavefronts per SIMD = six workgroups of 128
 // threads ... the register bound decides), 1024: 46 KiB (three workgroups per CU, as the quarter-wave kernel).
 // Envelope: fft_size 256 NW, 4 x 4, full band, even cyclic prefix, a constellation with a certificate or the slicer.
+// Round 7: the text above is the TIME-DOMAIN form (template parameter TD = true, option f64_threads = 265).  The default form leaves the
+// transmit side out -- the channel is flat, so only the noise is transformed and H X joins its spectrum in front of the decode: see the
+// comment at k_run_mimo_ofdm_pw.
 #include "mimo_planar_common.hpp"
 #include "walk_f64.hpp"
 
@@ -145,9 +148,20 @@ __device__ __forceinline__ void pw_first_stage(const unsigned char* lab_row, con
     }
 }
 
+// TD = false (the default form): THE SIGNAL IS ADDED AFTER THE RECEIVE TRANSFORM.  The channel is flat -- one H per realization -- so
+// by linearity of the DFT  fft(H T + sigma n) = H fft(T) + fft(sigma n)  and fft(T) is the symbols themselves times tx_scale N: the
+// transmit transform, its first radix-NW stage and its transposition carry X through ifft and fft back to itself and are not issued.
+// Only the noise (drawn in the time domain by the same ledger, same lane / register / sample map pw_mtime) goes through the receive
+// passes, the exchange and the last stage; lane (r, g) of wavefront jw then holds the NOISE spectrum of receive antenna r in register
+// q + NW uu, and lane (a, g) holds the labels of stream a at exactly those bins (byte q + NW uu of the decode's 16-byte read): one
+// look-up per register and  Y_r = sum_a H[r][a] X_a (tx_scale N) + noise  on v_mfma_f64_4x4x4 with the channel's own lane maps (A =
+// H[h mod 4][a], B = the lane's symbol, C = the noise spectrum).  DESIGN.md 5.14 has the scale and why no count moves.
+// TD = true (option f64_threads = 265): the time-domain form of round 6 -- transmit transform, channel on the samples -- kept as the
+// A/B partner and second witness.
 // ABL (MCLE_EXPERIMENTS builds only, option f64_variant: WRONG results by construction): 32 = no label draws / look-ups,
-// 64 = no transmit passes, 128 = no noise draws, 256 = no channel products, 512 = no receive passes, 1024 = no decode
-template <int NW, int DEC, int WPS, int ABL = 0>
+// 64 = no transmit passes (TD only: the default form has none, the bit switches nothing off there), 128 = no noise draws,
+// 256 = no channel products (TD) / no signal contraction (default form), 512 = no receive passes, 1024 = no decode
+template <int NW, int DEC, int WPS, bool TD = false, int ABL = 0>
 __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp, ModemParams<double> mp, uint64_t seed, uint64_t first,
                                                                    uint64_t count, const double2* __restrict__ g_tw,
                                                                    const double2* __restrict__ g_recs, mcle_counters* counters,
@@ -159,7 +173,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
     extern __shared__ __attribute__((aligned(16))) char pw_smem[];
     T* s_R = reinterpret_cast<T*>(pw_smem);                                  // [NW wavefronts][kPwPlane]: scratch plane of wavefront j
     cx<T>* s_table = reinterpret_cast<cx<T>*>(s_R + NW * kPwPlane);           // [tab_len] constellation
-    cx<T>* s_txtab = s_table + ((mp.M + 1) & ~1);                             // [tab_len] constellation x tx scale
+    cx<T>* s_txtab = s_table + ((mp.M + 1) & ~1);                             // [tab_len] constellation x tx scale (TD) / x tx scale N
     cx<T>* s_rec = s_txtab + ((mp.M + 1) & ~1);                               // [2][kRec + 1]
     unsigned* s_part = reinterpret_cast<unsigned*>(s_rec + 2 * (kRec + 1));  // [2][16][2]
     constexpr int kBm = (kBmLdsDoubles + 1) & ~1;
@@ -174,11 +188,14 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
     const uint64_t row = (uint64_t)pp.n_ofdm_sym * (N + cp);
     const T sigma = (T)sqrt(pp.noise_var);
     const T tx_scale = (T)(1.0 / sqrt((double)NT) / sqrt((double)(N + cp)));
+    // the receive passes are un-normalized and the record's G carries rx_scale = sqrt(N + cp) / N: a symbol that went through the
+    // un-normalized inverse and forward transforms comes back times N
+    const T tab_scale = TD ? tx_scale : tx_scale * (T)N;
     const uint32_t mask = (uint32_t)(mp.M - 1);
     for (int m = tid; m < mp.M; m += TB) {
         const cx<T> c = mp.g_table[m];
         s_table[m] = c;
-        s_txtab[m] = cscale(c, tx_scale);
+        s_txtab[m] = cscale(c, tab_scale);
     }
     bm_tables_to_lds(s_bm, tid, TB);
     __shared__ WgTotals totals;
@@ -254,7 +271,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
             }
             cx<T> v[16];
             // ---- S1: lane (a, g): the first-stage output of this wavefront's time class for k' = g + 16 u; compiled per class ----
-            {
+            if constexpr (TD) {
                 const int ln = opaque(lane);
                 const unsigned char* lab = s_lab + ln * kLabStride;                // (a * 16 + g) = lane
                 if constexpr (NW == 4) {
@@ -281,7 +298,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                 }
             }
             // ---- transmit transform, pass 1 (DIF spans 64, 16 of the 256-point transforms; registers to registers) ----
-            if constexpr (!(ABL & 64)) {
+            if constexpr (TD && !(ABL & 64)) {
                 const int g = opaque(lane) & 15;
                 R16Tw64<T> tw;
 #pragma unroll
@@ -302,7 +319,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                 for (int c = 0; c < 16; ++c) nw[c] = s_words_mine[c * 64 + ln];
             }
             // ---- transposition (a, g | u) -> (a, h | c): element g + 16 u = 16 h + c, re plane then im plane ----
-            {
+            if constexpr (TD) {
                 const int ln = opaque(lane);
                 const int a = ln >> 4, g = ln & 15;
                 const int wbase = pw_slot(a, g), rbase = pw_slot(a, 16 * g);       // element g + 16 u: wbase + 17 u; 16 g + c: rbase + c
@@ -320,12 +337,20 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                 for (int c = 0; c < 16; ++c) v[c] = mk<T>(xr[c], s_mine[rbase + c]);
             }
             // ---- pass 2 (spans 4, 1: sixteen consecutive elements, constant roots only) ----
-            if constexpr (!(ABL & 64)) {
+            if constexpr (TD && !(ABL & 64)) {
                 R16Tw64<T> none;
                 r16_pass<T, true, false, 0, false, true, true, false, true>(nullptr, nullptr, 0, none, nullptr, 0, v, v);
             }
+            // ---- default form: the noise alone, lane (r, h), register c = sample NW pw_mtime(h, c) + j of receive antenna r ----
+            if constexpr (!TD) {
+#pragma unroll
+                for (int c = 0; c < 16; ++c) {
+                    if constexpr (ABL & 128) v[c] = mk<T>((T)nw[c].x, sigma);
+                    else v[c] = cn_words(nw[c].x, nw[c].y, sigma, s_bm);
+                }
+            }
             // ---- channel: R_r = sum_a H[r][a] T_a + noise on v_mfma_f64_4x4x4 (pipeline_mimo_qw.hip: the lane maps) ----
-            {
+            if constexpr (TD) {
                 const int ln = opaque(lane);
                 const cx<T> hA = s_H[(ln & 3) * NT + (ln >> 4)];                   // H[h mod 4][a]
                 const T hre = hA.x, him = hA.y, nhim = -hA.y;
@@ -401,7 +426,8 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
 #pragma unroll
                     for (int uu = 0; uu < UU; ++uu) ei[jj][uu] = s_R[jj * kPwPlane + rpos + 16 * uu];
             }
-            // ---- last radix-NW stage for my UU elements (register q + NW uu = bin k' + 256 q), decode on the matrix cores, decisions ----
+            // ---- last radix-NW stage for my UU elements (register q + NW uu = bin k' + 256 q), [default form: the signal,] decode on
+            //      the matrix cores, decisions ----
             if constexpr (!(ABL & 1024)) {
                 const int ln = opaque(lane);
                 const int g = ln & 15;
@@ -441,8 +467,30 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                         v[2 * uu + 1] = csub(u0, u1);
                     }
                 }
+            }
+            {
+                const int ln = opaque(lane);
                 const uint4 L = *reinterpret_cast<const uint4*>(s_lab + ln * kLabStride + 16 * j);    // labels of my sixteen bins, stream a
                 const uint32_t wds[4] = {L.x, L.y, L.z, L.w};
+                // default form: Y_r = sum_a H[r][a] X_a + noise spectrum -- byte q + NW uu of L is stream a's label at the bin of register
+                // q + NW uu, lane (a, g) supplies H[h mod 4][a] and its symbol, lane (r, g) the noise and takes Y_r
+                if constexpr (!TD && !(ABL & 256)) {
+                    const cx<T> hA = s_H[(ln & 3) * NT + (ln >> 4)];               // H[h mod 4][a]
+                    const T hre = hA.x, him = hA.y, nhim = -hA.y;
+#pragma unroll
+                    for (int u = 0; u < 16; ++u) {
+                        const uint32_t lb = (wds[u >> 2] >> (8 * (u & 3))) & 0xFFu;
+                        cx<T> X;
+                        if constexpr (ABL & 32) X = mk<T>((T)lb, 1.0);
+                        else X = s_txtab[lb];
+                        T yr = __builtin_amdgcn_mfma_f64_4x4x4f64(hre, X.x, v[u].x, 0, 0, 0);
+                        T yi = __builtin_amdgcn_mfma_f64_4x4x4f64(him, X.x, v[u].y, 0, 0, 0);
+                        yr = __builtin_amdgcn_mfma_f64_4x4x4f64(nhim, X.y, yr, 0, 0, 0);
+                        yi = __builtin_amdgcn_mfma_f64_4x4x4f64(hre, X.y, yi, 0, 0, 0);
+                        v[u] = mk<T>(yr, yi);
+                    }
+                }
+                if constexpr (!(ABL & 1024)) {
                 const cx<T> gA = s_G[(ln & 3) * NR + (ln >> 4)];                   // G[h mod 4][r]
                 const T gre = gA.x, gim = gA.y, ngim = -gA.y;
 #pragma unroll
@@ -461,8 +509,14 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                     }
                     walk_decide<DEC, 4>(mp, s_table, nullptr, e, tx, se, be);
                 }
-            } else {
-                se += (unsigned)(er[0][0] + ei[NW - 1][UU - 1] == 0.5);
+                } else {
+                    T keep = er[0][0] + ei[NW - 1][UU - 1];
+                    if constexpr (!TD) {
+#pragma unroll
+                        for (int u = 0; u < 16; ++u) keep += v[u].x + v[u].y;
+                    }
+                    se += (unsigned)(keep == 0.5) + (wds[0] == 0x12345u);
+                }
             }
         }
         se = wave_sum_u32(se);
@@ -490,7 +544,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
     }
 }
 
-template <int NW, int WPS, int ABL = 0>
+template <int NW, int WPS, bool TD = false, int ABL = 0>
 static int launch_mimo_ofdm_pw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
                                mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit) {
     using T = double;
@@ -506,11 +560,11 @@ static int launch_mimo_ofdm_pw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uin
     const size_t lds = (size_t)NW * kPwPlane * sizeof(T) + (2 * tab_len + 2 * (kRec + 1)) * sizeof(cx<T>) + 64 * sizeof(unsigned) +
                        (size_t)((kBmLdsDoubles + 1) & ~1) * sizeof(double) + (size_t)64 * pw_lab_stride<NW>();
     MCLE_REQUIRE(lds + 512 <= (size_t)160 * 1024, "part-wave MIMO-OFDM kernel: %zu B of LDS do not fit", lds);
-    auto kern = k_run_mimo_ofdm_pw<NW, WDEC_SLICER, WPS, ABL>;
+    auto kern = k_run_mimo_ofdm_pw<NW, WDEC_SLICER, WPS, TD, ABL>;
     switch (dec) {
-        case WDEC_QAM_CERT: kern = k_run_mimo_ofdm_pw<NW, WDEC_QAM_CERT, WPS, ABL>; break;
-        case WDEC_QUAD_CERT: kern = k_run_mimo_ofdm_pw<NW, WDEC_QUAD_CERT, WPS, ABL>; break;
-        case WDEC_AXIS4_CERT: kern = k_run_mimo_ofdm_pw<NW, WDEC_AXIS4_CERT, WPS, ABL>; break;
+        case WDEC_QAM_CERT: kern = k_run_mimo_ofdm_pw<NW, WDEC_QAM_CERT, WPS, TD, ABL>; break;
+        case WDEC_QUAD_CERT: kern = k_run_mimo_ofdm_pw<NW, WDEC_QUAD_CERT, WPS, TD, ABL>; break;
+        case WDEC_AXIS4_CERT: kern = k_run_mimo_ofdm_pw<NW, WDEC_AXIS4_CERT, WPS, TD, ABL>; break;
         default: break;
     }
     MCLE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -519,6 +573,7 @@ static int launch_mimo_ofdm_pw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uin
     const int by_waves = WPS * 4 / NW;                         // wavefronts per SIMD x four SIMDs / wavefronts per workgroup
     if (per_cu > by_waves) per_cu = by_waves;
     const uint64_t resident = (uint64_t)ctx->n_cu * per_cu;
+    ctx->set_kernel("mimo_ofdm_pw<%d>/%s", NW, TD ? "time" : "freq");          // which form served the call (mcle_ctx_last_kernel)
     const uint64_t kSlice = 1ull << 20;          // realizations per record kernel + link kernel pair (553 MB of records; 2^18: three more tails per bench step, -0.6 %)
     const uint64_t slice = count < kSlice ? count : kSlice;
     void* recs = nullptr;
@@ -548,29 +603,40 @@ int run_mimo_ofdm_pw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed
         ModemParams<double> mp = pipe_modem<double>(ctx, cfg->demod_method);
         if (walk_dec_kind(ctx, mp) == WDEC_GENERIC) return MCLE_E_UNSUPPORTED;     // no certificate: the planar kernel's candidate grid
     }
+    // MCLE_OPT_F64_THREADS: 265 = the time-domain form (three wavefronts per SIMD); 262 / 264 = two wavefronts per SIMD; the
+    // ablations of the MCLE_EXPERIMENTS builds (option f64_variant) apply to whichever form the option selects
     const bool two = ctx->opt[MCLE_OPT_F64_THREADS] == 262 || ctx->opt[MCLE_OPT_F64_THREADS] == 264;
-    if (cfg->fft_size == 2048)       // eight wavefronts = 512 threads: one workgroup per CU (86 KiB of LDS), two wavefronts per SIMD
-        return launch_mimo_ofdm_pw<8, 2>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-    if (cfg->fft_size == 512) {
+    const bool td = ctx->opt[MCLE_OPT_F64_THREADS] == 265;
+    if (cfg->fft_size == 2048) {     // eight wavefronts = 512 threads: one workgroup per CU (86 KiB of LDS), two wavefronts per SIMD
+        return td ? launch_mimo_ofdm_pw<8, 2, true>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit)
+                  : launch_mimo_ofdm_pw<8, 2>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
+    }
 #ifdef MCLE_EXPERIMENTS
-        switch ((int)ctx->opt[MCLE_OPT_F64_VARIANT]) {
-#define MCLE_PW_ABL(V_) case V_: return launch_mimo_ofdm_pw<2, 3, V_>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-            MCLE_PW_ABL(32) MCLE_PW_ABL(64) MCLE_PW_ABL(128) MCLE_PW_ABL(256) MCLE_PW_ABL(512) MCLE_PW_ABL(1024) MCLE_PW_ABL(2016)
-#undef MCLE_PW_ABL
-            default: break;
-        }
+#define MCLE_PW_ABL(NW_, V_)                                                                                          \
+    case V_:                                                                                                          \
+        return td ? launch_mimo_ofdm_pw<NW_, 3, true, V_>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit)     \
+                  : launch_mimo_ofdm_pw<NW_, 3, false, V_>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
+#define MCLE_PW_ABLS(NW_)                                                                                             \
+    switch ((int)ctx->opt[MCLE_OPT_F64_VARIANT]) {                                                                    \
+        MCLE_PW_ABL(NW_, 32) MCLE_PW_ABL(NW_, 64) MCLE_PW_ABL(NW_, 128) MCLE_PW_ABL(NW_, 256) MCLE_PW_ABL(NW_, 512)   \
+        MCLE_PW_ABL(NW_, 1024) MCLE_PW_ABL(NW_, 2016)                                                                 \
+        default: break;                                                                                               \
+    }
+#else
+#define MCLE_PW_ABLS(NW_)
 #endif
+    if (cfg->fft_size == 512) {
+        MCLE_PW_ABLS(2)
+        if (td) return launch_mimo_ofdm_pw<2, 3, true>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
         return two ? launch_mimo_ofdm_pw<2, 2>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit)
                    : launch_mimo_ofdm_pw<2, 3>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
     }
+    MCLE_PW_ABLS(4)
+#undef MCLE_PW_ABLS
 #ifdef MCLE_EXPERIMENTS
-    switch ((int)ctx->opt[MCLE_OPT_F64_VARIANT]) {
-#define MCLE_PW_ABL(V_) case V_: return launch_mimo_ofdm_pw<4, 3, V_>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-        MCLE_PW_ABL(32) MCLE_PW_ABL(64) MCLE_PW_ABL(128) MCLE_PW_ABL(256) MCLE_PW_ABL(512) MCLE_PW_ABL(1024) MCLE_PW_ABL(2016)
 #undef MCLE_PW_ABL
-        default: break;
-    }
 #endif
+    if (td) return launch_mimo_ofdm_pw<4, 3, true>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
     return two ? launch_mimo_ofdm_pw<4, 2>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit)
                : launch_mimo_ofdm_pw<4, 3>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
 }

@@ -1156,6 +1156,7 @@ int mcle_run_flat_fading(mcle_ctx* ctx, int dtype, const mcle_flat_cfg* cfg, uin
 
 int mcle_run_mimo_ofdm(mcle_ctx* ctx, int dtype, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first,
                        uint64_t count, mcle_counters* d_counters, uint32_t* d_sym_err, uint32_t* d_bit_err) {
+    if (ctx) ctx->last_kernel[0] = 0;      // (the part-wave kernel names its size and form; the other kernels leave it empty)
     int rc = check_pipe(ctx, dtype, cfg ? cfg->demod_method : 0, cfg);
     if (rc) return rc;
     MCLE_REQUIRE(cfg->nt >= 1 && cfg->nt <= cfg->nr && cfg->nr <= 4, "fused MIMO pipeline: 1 <= Nt <= Nr <= 4 (got %d x %d)",
