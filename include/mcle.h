@@ -98,7 +98,20 @@ int mcle_ctx_device_info(mcle_ctx* ctx, int* n_cu, int* lds_bytes, char* name, i
  *                                             "mimo_channel_philox f64 4x4 lane" (even columns), "mimo_channel_philox generic"
  *   mcle_alamouti_decode                      "alamouti_decode pair" (Y and out aligned to a pair), "alamouti_decode elem"
  *   mcle_jakes_taps_philox                    "jakes_taps c64 x4" (complex64, even n, taps 16-byte aligned), "jakes_taps elem"
- * MCLE_OPT_STAGED_GENERIC = 1 selects the last-named (generic) form of each. */
+ * MCLE_OPT_STAGED_GENERIC = 1 selects the last-named (generic) form of each.
+ * Config 4 (mcle_run_mimo_ofdm): every launcher names itself, one tag per kernel instantiation of the product build (the decision
+ * form -- slicer or which certificate -- is a template argument of the wave kernels too and is NOT in the tag):
+ *   "mimo_ofdm_pw<NW>/freq", ".../time"        part-wave, NW = 2 / 4 / 8 wavefronts per realization (512 / 1024 / 2048), the round-7 form /
+ *                                             the time-domain form; suffix "/w2" = registers bounded for two wavefronts per SIMD where
+ *                                             three is the default (NW = 2: f64_threads 262, NW = 4: 264; NW = 8 has the one bound)
+ *   "mimo_ofdm_fw<NA> f64|f32 w<WPS>"          full-wave at 256 points, NA x NA antennas, wavefronts per SIMD the registers are bounded for
+ *   "mimo_ofdm_qw w<WPS>"                      quarter-wave (complex128, 1024, 4x4)
+ *   "mimo_ofdm_planar<N,NT,NR> f64|f32 ah<AH> w<WPS> v<VARIANT>"   the planar family: antennas per thread, wavefronts per SIMD, variant
+ *                                             (0 = radix-4 stages; radix-16 passes: 4 = separate channel stage, 12 = fused, 28 = fused
+ *                                             with every layer-1 twiddle from the table)
+ *   "mimo_ofdm_mfma v<36|32|30|21>"            the complex64 matrix-core kernel and its variant
+ *   "mimo_ofdm_generic<N,NA> f64|f32"          the generic radix-4 kernel (2x2 / 4x4, 64 .. 2048)
+ * "" after a refused call. */
 int mcle_ctx_last_kernel(mcle_ctx* ctx, char* name, int len);
 int mcle_malloc(mcle_ctx* ctx, size_t bytes, void** d_ptr);
 int mcle_free(mcle_ctx* ctx, void* d_ptr);
@@ -122,7 +135,11 @@ enum {
     MCLE_OPT_TDL_MFMA_WAVES = 5,   /* config-3 matrix-core kernel: 0 / 2 = two waves per SIMD, 3 = three, 32 = three with two
                                       realizations per pass instead of four */
     MCLE_OPT_JAKES_DIRECT = 6,     /* 1: one sincos per ray and sample (jakes_generate: k_jakes; complex128 flat-fading pipeline: no rotation recurrence) */
-    MCLE_OPT_F64_GENERIC = 7,      /* 1: config 4 on the generic radix-4 kernel instead of the planar family (either arithmetic) */
+    MCLE_OPT_F64_GENERIC = 7,      /* 1: config 4 on the generic radix-4 kernel instead of the planar family and the wave kernels (either
+                                      arithmetic) WHERE THAT KERNEL EXISTS: Nt = Nr in {2, 4}; every other geometry still runs the planar
+                                      family -- like no_mfma, the option selects a kernel and does not shrink the envelope.  (2048, 4x4)
+                                      in complex128 is refused with it: the generic kernel needs 168 KiB of LDS there.  f32_mfma = 1
+                                      comes first at complex64 (1024, 4x4). */
     MCLE_OPT_F64_THREADS = 8,      /* complex128 config-4 kernel at (1024, 4x4): 0 = the quarter-wave kernel (round 6,
                                       csrc/pipeline_mimo_qw.hip: a wavefront owns one time class n mod 4 of all antennas, samples in
                                       registers between radix-16 passes, three workgroups per CU, the channel contraction on
@@ -143,8 +160,11 @@ enum {
                                       csrc/pipeline_mimo_fw.hip, one realization per wavefront) / the half-wave kernel (512:
                                       csrc/pipeline_mimo_pw.hip, two wavefronts per realization), both with channel AND decode on
                                       v_mfma_f64_4x4x4; 262 = bounded for two wavefronts per SIMD; 261 = the planar radix-4 form of
-                                      rounds 3-5; (256, 2x2): the full-wave kernel with two realizations per wavefront; (2048, 4x4): the
-                                      eighth-wave kernel (512 threads).  (1024, 4x4): since the end of round 6 the DEFAULT (0) is the
+                                      rounds 3-5 (in fact any value but 0 / 260 / 262; at 512 and 2048 any but 0 / 260 / 262 / 265); both
+                                      arithmetics at 256 (complex64: 0 = two wavefronts per SIMD, 262 = three); (256, 2x2): the full-wave
+                                      kernel with two realizations per wavefront, and with 261 or outside the envelope the GENERIC
+                                      kernel -- the planar family has no (256, 2x2) kernel, the generic one is faster there;
+                                      (2048, 4x4): the eighth-wave kernel (512 threads, one register bound: 262 = 0).  (1024, 4x4): since the end of round 6 the DEFAULT (0) is the
                                       quarter-wave decomposition with the decode on the matrix cores as well (pipeline_mimo_pw.hip,
                                       NW = 4; 263 = the same, explicit; 264 = two wavefronts per SIMD); 260 / 262 select the first
                                       quarter-wave kernel (pipeline_mimo_qw.hip, VALU decode).
@@ -152,7 +172,10 @@ enum {
                                       receive transform -- the channel is flat, so only the noise is transformed and H X joins it
                                       on v_mfma_f64_4x4x4 in front of the decode; 265 = its time-domain form of round 6 (transmit
                                       transform, channel on the samples) at all three sizes, same counts: the A/B partner.
-                                      mcle_ctx_last_kernel names the size and the form: "mimo_ofdm_pw<NW>/freq" or ".../time". */
+                                      (1024, Nt < 4, Nr = 4), either arithmetic: 0 = the radix-16 form, any other value the radix-4 one.
+                                      mcle_ctx_last_kernel names the kernel that served the call -- for the part-wave kernel the size
+                                      and the form, "mimo_ofdm_pw<NW>/freq" or ".../time" (+ "/w2" at the two-wavefront bound); the
+                                      whole grammar is listed there. */
     MCLE_OPT_BD_RUNTIME_SOLVE = 9, /* 1: the block-diagonalisation pipeline solves with the run-time-sized routine (private
                                       arrays in scratch) also where the compile-time-sized one (K nr <= 6) applies */
     MCLE_OPT_DEMOD_NOCERT = 10,    /* 1: min-distance decisions of a square Gray QAM always through the table search (candidate
@@ -551,7 +574,8 @@ int mcle_run_ofdm_tdl(mcle_ctx* ctx, int dtype, const mcle_ofdm_tdl_cfg* cfg, ui
                       uint32_t* d_sym_err, uint32_t* d_bit_err);
 /* Envelope: 1 <= Nt <= Nr <= 4, either arithmetic: fft_size 256 / 512 / 1024 / 2048 with every Nt <= Nr (Blast takes any Nr x Nt,
  * mimo/mimo.py:264-309) on the planar kernel family (pipeline_mimo_planar.hip; in complex128 2048 with 4 receive antennas exists
- * there only: 148 KiB of LDS); 2x2 / 4x4 at 64 and 128 on the generic kernel.  complex64 at (1024, 4x4): the planar radix-16
+ * there only: 148 KiB of LDS) -- Nr >= 2: the family has no 1x1 geometry, which is refused at every size; 2x2 / 4x4 at 64 and 128 on
+ * the generic kernel.  complex64 at (1024, 4x4): the planar radix-16
  * kernel by default, the matrix-core kernel with MCLE_OPT_F32_MFMA = 1.  Anything else: MCLE_E_INVAL. */
 int mcle_run_mimo_ofdm(mcle_ctx* ctx, int dtype, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed,
                        uint64_t first, uint64_t count, mcle_counters* d_counters,

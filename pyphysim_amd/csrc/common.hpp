@@ -256,7 +256,7 @@ struct mcle_ctx {
 
     // kernel-selection options (mcle_ctx_set_option); 0 = default
     long long opt[MCLE_OPT_COUNT] = {};
-    // which kernel served the last config-3 / f1 call or staged operator with more than one form (mcle_ctx_last_kernel;
+    // which kernel served the last config-3 / f1 / config-4 call or staged operator with more than one form (mcle_ctx_last_kernel;
     // host-only diagnostic): cleared on entry, set where the chosen kernel launches
     char last_kernel[48] = {};
     void set_kernel(const char* fmt, ...) {

@@ -387,6 +387,7 @@ static int launch_mimo_ofdm_fw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uin
         case WDEC_AXIS4_CERT: kern = k_run_mimo_ofdm_fw<T, NA, WDEC_AXIS4_CERT, WPS, ABL>; break;
         default: break;
     }
+    ctx->set_kernel("mimo_ofdm_fw<%d> %s w%d", NA, sizeof(T) == 8 ? "f64" : "f32", WPS);
     MCLE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int per_cu = (int)((size_t)160 * 1024 / (lds + 512));
     if (per_cu < 1) per_cu = 1;

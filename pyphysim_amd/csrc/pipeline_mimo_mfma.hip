@@ -509,6 +509,7 @@ int run_mimo_ofdm_mfma(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uint64_t se
     const int waves = variant / 10 == 2 ? 2 : 3;
     auto kern = variant == 30 ? k_run_mimo_ofdm_mfma<3, 0> : variant == 21 ? k_run_mimo_ofdm_mfma<2, 1>
                 : variant == 32 ? k_run_mimo_ofdm_mfma<3, 2> : k_run_mimo_ofdm_mfma<3, 6>;
+    ctx->set_kernel("mimo_ofdm_mfma v%d", variant);
     MCLE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int per_cu = (int)((size_t)160 * 1024 / (lds + 512));
     if (per_cu < 1) per_cu = 1;

@@ -489,6 +489,7 @@ static int launch_mimo_ofdm_planar(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg,
     MCLE_REQUIRE(lds + 512 <= (size_t)160 * 1024, "planar MIMO-OFDM kernel: %zu B of LDS do not fit (fft_size %d, %d receive antennas)",
                  lds, N, NR);
     auto kern = k_run_mimo_ofdm_planar<T, N, NT, NR, AH, WPS, VAR>;
+    ctx->set_kernel("mimo_ofdm_planar<%d,%d,%d> %s ah%d w%d v%d", N, NT, NR, sizeof(T) == 8 ? "f64" : "f32", AH, WPS, VAR);
     MCLE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int per_cu = (int)((size_t)160 * 1024 / (lds + 512));
     const int by_waves = (WPS * 256) / TB > 0 ? (WPS * 256) / TB : 1;          // what __launch_bounds__ allocated registers for
@@ -519,7 +520,7 @@ static int launch_mimo_ofdm_planar(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg,
 //   1024  4x4   radix-16 form: 4 antennas / wave-per-antenna, 256 threads, 2 workgroups per CU, 2 wavefronts per SIMD
 //  (1024  4x4   2   512   2   4  radix-4, option f64_threads=512)   2048  4x4   2  1024   1   4        512  4x4   2   256   3   3        256  4x4   2  128  5  3
 //   1024  2x2   2   256   3   3        2048  2x2   2   512   2   4        512  2x2   2   128   5   3        256  2x2   2   64  8  2
-// Nt < Nr (mimo/mimo.py:264-309 takes any): every 1 <= Nt <= Nr <= 4 at every size runs the Nr geometry (Nr = 3: three
+// Nt < Nr (mimo/mimo.py:264-309 takes any): every 1 <= Nt <= Nr <= 4 with Nr >= 2 at every size runs the Nr geometry (Nr = 3: three
 // antennas per thread, one group); antenna groups past Nt idle in the IFFT.
 // complex64 (round 4): the same kernels on planes of floats.  Half the LDS per workgroup, 80 - 140 registers per thread where
 // complex128 takes 120 - 250: the radix-4 geometries keep the complex128 table's wavefronts-per-SIMD bound (doubling it spilled
@@ -565,11 +566,12 @@ static int run_mimo_ofdm_planar_t(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, 
     // 10.66 ms per 262 144 realizations against 11.65 for the 512-thread radix-4 form and 12.15 for the 256-thread one,
     // profiles/r04/c4_f64_r16_ab.log).  MCLE_OPT_F64_THREADS: 512 = radix-4, two antennas per thread; 256 = radix-4, four
     // antennas per thread, twiddles in registers.  MCLE_OPT_F64_VARIANT 1 .. 3: timing bounds on the 512-thread form.
-    if (n == 256 && nt == nr && (nt == 4 || nt == 2)) {
+    if (n == 256 && nt == 4 && nr == 4) {    // ((256, 2 x 2) never comes here: mcle_run_mimo_ofdm tries the full-wave kernel itself, then the generic one)
         {   // (either arithmetic since the last day of round 6: complex64 contracts on the VALU, pipeline_mimo_fw.hip)
             // round 6: the FULL-WAVE kernel (pipeline_mimo_fw.hip: a realization is one wavefront -- the quarter-wave kernel's register
             // passes without its radix-4 exchange stage, channel AND decode on v_mfma_f64_4x4x4, no workgroup barrier).
-            // MCLE_OPT_F64_THREADS = 261: the planar radix-4 form of rounds 3-5; 262: full-wave bounded for two wavefronts per SIMD.
+            // MCLE_OPT_F64_THREADS = 261 (any value but 0 / 260 / 262): the planar radix-4 form of rounds 3-5; 262: full-wave at the
+            // other wavefront bound (complex128 two per SIMD instead of three, complex64 three instead of two).
             const long long thr = ctx->opt[MCLE_OPT_F64_THREADS];
             if (thr == 0 || thr == 260 || thr == 262) {
                 const int rq = run_mimo_ofdm_fw(ctx, F64 ? MCLE_F64 : MCLE_F32, cfg, seed, first, count, d_counters, d_sym, d_bit);
@@ -653,10 +655,12 @@ static int run_mimo_ofdm_planar_t(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, 
     }
     // every Nt <= Nr <= 4 at every size: Nr = 2 / 4 two antennas per thread, Nr = 3 three (one group)
 #define MCLE_F64_SIZE(N_, W2_, W4_)                                                                                  \
-    MCLE_F64_GEOM(N_, 1, 2, 2, W2_) MCLE_F64_GEOM(N_, 2, 2, 2, W2_)                                                  \
+    MCLE_F64_GEOM(N_, 2, 2, 2, W2_) MCLE_F64_SIZE_REST(N_, W2_, W4_)
+#define MCLE_F64_SIZE_REST(N_, W2_, W4_)                                                                             \
+    MCLE_F64_GEOM(N_, 1, 2, 2, W2_)                                                                                  \
     MCLE_F64_GEOM(N_, 1, 3, 3, 2) MCLE_F64_GEOM(N_, 2, 3, 3, 2) MCLE_F64_GEOM(N_, 3, 3, 3, 2)                        \
     MCLE_F64_GEOM(N_, 1, 4, 2, W4_) MCLE_F64_GEOM(N_, 2, 4, 2, W4_) MCLE_F64_GEOM(N_, 3, 4, 2, W4_)
-    MCLE_F64_SIZE(256, 2, 3) MCLE_F64_GEOM(256, 4, 4, 2, 3)
+    MCLE_F64_SIZE_REST(256, 2, 3) MCLE_F64_GEOM(256, 4, 4, 2, 3)      // (no (256, 2 x 2): the generic kernel is the faster one, see mcle_run_mimo_ofdm)
     MCLE_F64_SIZE(512, 3, 3) MCLE_F64_GEOM(512, 4, 4, 2, 3)
     if (n == 1024 && nr == 4 && ctx->opt[MCLE_OPT_F64_THREADS] == 0) {      // Nt < 4 at the benchmark size: the radix-16 form too
         constexpr int WR16 = F64 ? 2 : 4, VR16 = F64 ? 12 : 4;       // complex128: fused, 2 workgroups per CU; complex64: unfused, 4
@@ -683,13 +687,13 @@ static int run_mimo_ofdm_planar_t(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, 
     }
     MCLE_F64_SIZE(2048, 4, 4) MCLE_F64_GEOM(2048, 4, 4, 2, 4)
 #undef MCLE_F64_SIZE
+#undef MCLE_F64_SIZE_REST
 #undef MCLE_F64_GEOM
     return MCLE_E_UNSUPPORTED;
 }
 
 int run_mimo_ofdm_planar(mcle_ctx* ctx, int dtype, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
                          mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit) {
-    if (ctx->opt[MCLE_OPT_F64_GENERIC]) return MCLE_E_UNSUPPORTED;
     return dtype == MCLE_F32 ? run_mimo_ofdm_planar_t<float>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit)
                              : run_mimo_ofdm_planar_t<double>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
 }

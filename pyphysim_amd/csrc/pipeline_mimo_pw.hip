@@ -573,7 +573,8 @@ static int launch_mimo_ofdm_pw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uin
     const int by_waves = WPS * 4 / NW;                         // wavefronts per SIMD x four SIMDs / wavefronts per workgroup
     if (per_cu > by_waves) per_cu = by_waves;
     const uint64_t resident = (uint64_t)ctx->n_cu * per_cu;
-    ctx->set_kernel("mimo_ofdm_pw<%d>/%s", NW, TD ? "time" : "freq");          // which form served the call (mcle_ctx_last_kernel)
+    // which form served the call (mcle_ctx_last_kernel); "/w2": the two-wavefront register bound where three is the default (NW = 2, 4)
+    ctx->set_kernel("mimo_ofdm_pw<%d>/%s%s", NW, TD ? "time" : "freq", WPS == (NW == 8 ? 2 : 3) ? "" : "/w2");
     const uint64_t kSlice = 1ull << 20;          // realizations per record kernel + link kernel pair (553 MB of records; 2^18: three more tails per bench step, -0.6 %)
     const uint64_t slice = count < kSlice ? count : kSlice;
     void* recs = nullptr;

@@ -464,6 +464,7 @@ static int launch_mimo_ofdm_qw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uin
                        kQwLabBytes + 16;
     MCLE_REQUIRE(lds + 512 <= (size_t)160 * 1024, "quarter-wave MIMO-OFDM kernel: %zu B of LDS do not fit", lds);
     auto kern = k_run_mimo_ofdm_qw<WPS, ABL>;
+    ctx->set_kernel("mimo_ofdm_qw w%d", WPS);
     MCLE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int per_cu = (int)((size_t)160 * 1024 / (lds + 512));
     if (per_cu < 1) per_cu = 1;

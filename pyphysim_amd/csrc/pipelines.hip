@@ -1031,6 +1031,7 @@ int run_mimo_impl(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, u
                        (size_t)NA * cfg->num_used;
     MCLE_REQUIRE(lds <= 160 * 1024, "configuration needs %zu bytes of LDS (limit 160 KiB)", lds);
     auto kern = k_run_mimo_ofdm<T, N, NA>;
+    ctx->set_kernel("mimo_ofdm_generic<%d,%d> %s", N, NA, sizeof(T) == 8 ? "f64" : "f32");
     void* filters = nullptr;
     MCLE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int per_cu = (int)((size_t)160 * 1024 / (lds + 512));  // gfx950: 160 KiB of LDS per CU
@@ -1156,7 +1157,7 @@ int mcle_run_flat_fading(mcle_ctx* ctx, int dtype, const mcle_flat_cfg* cfg, uin
 
 int mcle_run_mimo_ofdm(mcle_ctx* ctx, int dtype, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first,
                        uint64_t count, mcle_counters* d_counters, uint32_t* d_sym_err, uint32_t* d_bit_err) {
-    if (ctx) ctx->last_kernel[0] = 0;      // (the part-wave kernel names its size and form; the other kernels leave it empty)
+    if (ctx) ctx->last_kernel[0] = 0;      // (every launcher below names itself before it launches: mcle_ctx_last_kernel, grammar in mcle.h)
     int rc = check_pipe(ctx, dtype, cfg ? cfg->demod_method : 0, cfg);
     if (rc) return rc;
     MCLE_REQUIRE(cfg->nt >= 1 && cfg->nt <= cfg->nr && cfg->nr <= 4, "fused MIMO pipeline: 1 <= Nt <= Nr <= 4 (got %d x %d)",
@@ -1174,14 +1175,16 @@ int mcle_run_mimo_ofdm(mcle_ctx* ctx, int dtype, const mcle_mimo_ofdm_cfg* cfg, 
         rc = run_mimo_ofdm_mfma(ctx, cfg, seed, first, count, d_counters, d_sym_err, d_bit_err);
         if (rc != MCLE_E_UNSUPPORTED) return rc;
     }
-    // the planar kernel family (pipeline_mimo_planar.hip: FFT 256 .. 2048, 1 <= Nt <= Nr <= 4).  no_mfma = 1 keeps complex64 on the
-    // round-1 generic kernel below WHERE THAT ONE EXISTS (Nt = Nr in {2, 4}); every other geometry still runs the planar family --
-    // the option selects a kernel, it does not shrink the envelope
+    // the planar kernel family (pipeline_mimo_planar.hip: FFT 256 .. 2048, 1 <= Nt <= Nr <= 4).  no_mfma = 1 (complex64) and f64_generic = 1
+    // (either arithmetic) keep the call on the round-1 generic kernel below WHERE THAT ONE EXISTS (Nt = Nr in {2, 4}); every other
+    // geometry still runs the planar family -- an option selects a kernel, it does not shrink the envelope
     const bool generic_has_it = cfg->nt == cfg->nr && (cfg->nt == 2 || cfg->nt == 4);
+    const bool want_generic = generic_has_it && (ctx->opt[MCLE_OPT_F64_GENERIC] || (dtype == MCLE_F32 && ctx->opt[MCLE_OPT_NO_MFMA]));
     // 2x2 at 256 points: the generic kernel (four realizations per 256-thread workgroup) is the faster one -- 1.65 against 1.06e8
-    // realizations/s in complex64, 1.01 against 0.98e8 in complex128 (profiles/r05/f32_family_rates.json, f64_family_rates.json)
+    // realizations/s in complex64, 1.01 against 0.98e8 in complex128 (profiles/r05/f32_family_rates.json, f64_family_rates.json): the
+    // planar family has no kernel of this shape
     const bool generic_is_faster = cfg->fft_size == 256 && cfg->nt == 2 && cfg->nr == 2;
-    if (generic_is_faster && !(dtype == MCLE_F32 && ctx->opt[MCLE_OPT_NO_MFMA])) {
+    if (generic_is_faster && !want_generic) {
         // ... and since round 6 the full-wave kernel (pipeline_mimo_fw.hip, two realizations per wavefront) beats both inside its envelope
         const long long thr = ctx->opt[MCLE_OPT_F64_THREADS];
         if (thr == 0 || thr == 260 || thr == 262) {
@@ -1189,13 +1192,13 @@ int mcle_run_mimo_ofdm(mcle_ctx* ctx, int dtype, const mcle_mimo_ofdm_cfg* cfg, 
             if (rc != MCLE_E_UNSUPPORTED) return rc;
         }
     }
-    if (!(dtype == MCLE_F32 && ctx->opt[MCLE_OPT_NO_MFMA] && generic_has_it) && !generic_is_faster) {
+    if (!want_generic && !generic_is_faster) {
         rc = run_mimo_ofdm_planar(ctx, dtype, cfg, seed, first, count, d_counters, d_sym_err, d_bit_err);
         if (rc != MCLE_E_UNSUPPORTED) return rc;
     }
     MCLE_REQUIRE(cfg->nt == cfg->nr && (cfg->nt == 2 || cfg->nt == 4),
                  "fused MIMO pipeline: %d x %d at fft_size %d is outside the envelope (2x2 / 4x4 at 64 .. 2048 in both arithmetics; "
-                 "every 1 <= Nt <= Nr <= 4 at 256 .. 2048)", cfg->nt, cfg->nr, cfg->fft_size);
+                 "every 1 <= Nt <= Nr <= 4 with Nr >= 2 at 256 .. 2048)", cfg->nt, cfg->nr, cfg->fft_size);
 #define MCLE_RUN(N_, NA_)                                                                                         \
     if (cfg->fft_size == N_ && cfg->nt == NA_)                                                                    \
         return dtype == MCLE_F32                                                                                  \

@@ -125,8 +125,10 @@ class Engine:
             self.lib.mcle_free(self.ctx, ptr)
 
     def last_kernel(self):
-        """Diagnostic: the tag of the kernel that served this engine's last config-3 / f1 call (run_ofdm_tdl,
-        run_mimo_ofdm_tdl), e.g. 'siso_wave N=1024 K=6' or 'mimo_coop'; '' before such a call and after a refused one."""
+        """Diagnostic: the tag of the kernel that served this engine's last config-3 / f1 / config-4 call (run_ofdm_tdl,
+        run_mimo_ofdm_tdl, run_mimo_ofdm), e.g. 'siso_wave N=1024 K=6', 'mimo_coop', 'mimo_ofdm_pw<4>/freq' or
+        'mimo_ofdm_planar<1024,4,4> f32 ah4 w4 v4', or the form of the last staged operator that has more than one (the grammar:
+        include/mcle.h at mcle_ctx_last_kernel); '' before such a call and after a refused one."""
         buf = ctypes.create_string_buffer(64)
         check(self.lib.mcle_ctx_last_kernel(self.ctx, buf, 64))
         return buf.value.decode()

@@ -2,7 +2,7 @@
 realization per wavefront; csrc/pipeline_mimo_pw.hip with NW = 2 / 8: two / eight wavefronts per realization at 512 / 2048; channel and decode on
 v_mfma_f64_4x4x4; the defaults of mcle_run_mimo_ofdm at these sizes for 4 x 4, full band, even cyclic prefix, decisions by slicer or
 certificate since round 6; option f64_threads = 260 asks for them explicitly, 262 bounds the registers for two wavefronts per
-SIMD, 261 selects the planar kernel they replaced), and the same decomposition at 1024 with the decode on the matrix cores
+SIMD, 261 selects the planar kernel they replaced -- at (256, 2 x 2) the generic kernel), and the same decomposition at 1024 with the decode on the matrix cores
 (pipeline_mimo_pw.hip with NW = 4, f64_threads = 263 / 264; the quarter-wave kernel pipeline_mimo_qw.hip stays the default there) -- per-realization symbol AND bit error counts equal to the oracle
 chain's (oracle/chains.py::chain_mimo_ofdm) on every corner of its envelope, equal to the planar kernel's over two thousand
 realizations per case, and requests outside the envelope served by the planar kernel.
@@ -133,7 +133,7 @@ def _run22(engine, kw, first, count, method, threads):
 @pytest.mark.parametrize("case", range(len(INSIDE) + len(OUTSIDE)))
 def test_two_by_two_counts_equal_the_oracle(engine, case):
     """Odd and even counts (an odd count leaves the last wavefront's second half without a realization), every corner of the envelope
-    and requests outside it, all four kernel selections."""
+    and requests outside it, all four kernel selections (261 and outside the envelope: the generic kernel)."""
     kw = (INSIDE + OUTSIDE)[case]
     _set(engine, kw)
     for first, count in (((1 << 36) + 77, 23), (5, 1), (900, 8)):
@@ -149,9 +149,10 @@ def test_two_by_two_counts_equal_the_oracle(engine, case):
                 assert res["sym_errors"] == int(want_se.sum()) and res["sym_errors_sq"] == int((want_se.astype(np.int64) ** 2).sum())
 
 
-def test_two_by_two_against_the_oracle_and_the_planar_kernel_at_depth(engine):
+def test_two_by_two_against_the_oracle_and_the_generic_kernel_at_depth(engine):
     """(256, 2 x 2), 64-QAM, 22 dB: 4 097 realizations (an odd count) against the oracle, both demodulators and register bounds; the
-    planar kernel on the same range; zero forcing at infinite SNR skips what the planar kernel skips."""
+    GENERIC kernel on the same range (f64_threads = 261 -- the planar family has no (256, 2 x 2) kernel: mimo_ofdm_generic<256,2>,
+    tests/test_gpu_c4_edges.py); zero forcing at infinite SNR skips what the generic kernel skips."""
     kw = dict(mod="qam", M=64, snr_db=22.0)
     _set(engine, kw)
     first, count = 424242, 4097
