@@ -279,12 +279,18 @@ def chain_ia(rng, mod='qam', M=16, K=3, nr=2, nt=2, Ns=1, NSymbs=200, snr_db=20.
     return _counts(out, idx, dec, M)
 
 
-def chain_mimo_scheme(rng, scheme='blast', mod='qam', M=16, nt=2, nr=2, NSymbs=200, snr_db=15.0):
+def chain_mimo_scheme(rng, scheme='blast', mod='qam', M=16, nt=2, nr=2, NSymbs=200, snr_db=15.0, mmse=False,
+                      canonical=False):
     """apps/mimo/simulate_mimo.py:68-142: flat channel randn_c(Nr, Nt) per realization, one of the six MIMO
     schemes (Alamouti / Blast / MRC / MRT / SVDMimo / GMDMimo -- set_channel_matrix only, i.e. zero forcing),
-    NSymbs symbols per layer, single carrier."""
+    NSymbs symbols per layer, single carrier.
+    mmse=True: the noise variance goes into the receive filter of Blast / MRC / GMDMimo (set_noise_var, mimo.py:577-607),
+    the other schemes have no such filter.  canonical=True: SVDMimo / GMDMimo with the device routine's singular-vector
+    phases (omimo.canonical_svd) instead of LAPACK's -- the same link up to one phase per stream, hence other noise
+    samples per decision: the HIP kernels' decisions, not the reference's."""
     table = constellation(mod, M)
     noise_var = 1.0 / float(omodem.dB2Linear(snr_db))
+    filter_nv = noise_var if mmse else 0.0
     H = rng.cn(philox.STREAM_CHAN, nr, nt)
     layers = {'blast': nt, 'mrc': nt, 'svd': nt, 'gmd': nt, 'alamouti': 1, 'mrt': 1}[scheme]
     idx = rng.symbols(NSymbs * layers, M)
@@ -295,6 +301,9 @@ def chain_mimo_scheme(rng, scheme='blast', mod='qam', M=16, nt=2, nr=2, NSymbs=2
         X = omimo.alamouti_encode(sym)
     elif scheme == 'mrt':
         X = omimo.mrt_encode(sym, H)
+    elif canonical and scheme in ('svd', 'gmd'):
+        W, G_H = omimo.scheme_filters(scheme, H, filter_nv, canonical=True)
+        X = W @ sym.reshape(nt, -1)
     elif scheme == 'svd':
         X = omimo.svd_encode(sym, H)
     else:
@@ -302,19 +311,21 @@ def chain_mimo_scheme(rng, scheme='blast', mod='qam', M=16, nt=2, nr=2, NSymbs=2
     noise = rng.cn(philox.STREAM_NOISE, nr, NSymbs)
     Y = H @ X + math.sqrt(noise_var) * noise
     if scheme in ('blast', 'mrc'):
-        est = omimo.blast_decode(Y, H, 0.0)
+        est = omimo.blast_decode(Y, H, filter_nv)
     elif scheme == 'alamouti':
         est = omimo.alamouti_decode(Y, H)
     elif scheme == 'mrt':
         est = omimo.mrt_decode(Y, H)
+    elif canonical and scheme in ('svd', 'gmd'):
+        est = (G_H @ Y).reshape(-1)
     elif scheme == 'svd':
         est = omimo.svd_decode(Y, H)
     else:
-        est = omimo.gmd_decode(Y, H, 0.0)
+        est = omimo.gmd_decode(Y, H, filter_nv)
     dec = omodem.demodulate(table, est)
     out = dict(table=table, H=H, idx=idx, noise=noise, est=est, noise_var=noise_var)
     if scheme in ('svd', 'gmd'):      # the basis-dependent pair (mimo.py:846-890, 965-1011), as minted into the fixture
-        out['W'], out['G_H'] = omimo.scheme_filters(scheme, H)
+        out['W'], out['G_H'] = omimo.scheme_filters(scheme, H, filter_nv, canonical=canonical)
     return _counts(out, idx, dec, M)
 
 

@@ -137,16 +137,35 @@ def gmd(U, S, V_H):
     return Q, R, P
 
 
-def scheme_filters(scheme, H):
-    """(precoder W, receive filter G_H) of SVDMimo / GMDMimo for channel H with NumPy's (LAPACK's) singular vectors:
-    mimo.py:846-890 (W = V / sqrt(Nt), G_H = diag(1/S) U^H sqrt(Nt)) and :965-1011 (W = P / sqrt(Nt), Blast's zero-forcing
-    filter of Q R)."""
-    nt = H.shape[1]
+def canonical_svd(H):
+    """(U, S, V_H) of H with S descending and the singular-vector phases of the device routine (csrc/mimo_svd.hpp,
+    jacobi_svd): the largest-magnitude entry of every right singular vector is real and positive (the first one on ties),
+    the left vector turned by the same phase.  numpy.linalg.svd's pair brought to that convention: column c of V and of U
+    times conj(piv) / |piv|, piv the pivot entry of V[:, c] -- still an SVD of H, and a function of H alone wherever the
+    singular values are distinct and the pivot is unique."""
     U, S, V_H = np.linalg.svd(H)
+    U = np.array(U, dtype=complex)
+    V = np.array(V_H.conj().T, dtype=complex)
+    for c in range(V.shape[1]):
+        piv = V[int(np.argmax(np.abs(V[:, c]))), c]        # argmax: the first of equal maxima
+        rot = np.conj(piv) / abs(piv)
+        V[:, c] *= rot
+        if c < U.shape[1]:
+            U[:, c] *= rot
+    return U, S, V.conj().T
+
+
+def scheme_filters(scheme, H, noise_var=0.0, canonical=False):
+    """(precoder W, receive filter G_H) of SVDMimo / GMDMimo for channel H: mimo.py:846-890 (W = V / sqrt(Nt),
+    G_H = diag(1/S) U^H sqrt(Nt)) and :965-1011 (W = P / sqrt(Nt), Blast's filter of Q R: zero forcing, or MMSE when
+    noise_var > 0).  canonical=False: NumPy's (LAPACK's) singular vectors, as the reference has them; canonical=True:
+    the device routine's phases (canonical_svd), i.e. the filters the HIP kernels build, entry by entry."""
+    nt = H.shape[1]
+    U, S, V_H = canonical_svd(H) if canonical else np.linalg.svd(H)
     if scheme == 'svd':
         return V_H.conj().T / math.sqrt(nt), np.diag(1.0 / S) @ U.conj().T * math.sqrt(nt)
     Q, R, P = gmd(U, S, V_H)
-    return P / math.sqrt(nt), blast_receive_filter(Q @ R, 0.0)
+    return P / math.sqrt(nt), blast_receive_filter(Q @ R, noise_var)
 
 
 def gmd_encode(x, H):

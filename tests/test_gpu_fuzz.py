@@ -18,6 +18,9 @@ N_MFMA_TRIALS_EARLY = int(os.environ.get("MCLE_FUZZ_TRIALS", "10"))
 MODS = [("bpsk", 2), ("qpsk", 4), ("psk", 8), ("psk", 16), ("qam", 4), ("qam", 16), ("qam", 64), ("qam", 256)]
 
 
+FLAT_SCHEMES = [("blast", 2, 3), ("blast", 4, 4), ("mrc", 1, 4), ("mrt", 3, 1), ("alamouti", 2, 2)]
+
+
 def _bind(engine, mod, M):
     engine.set_constellation(chains.constellation(mod, M), _lib.CONST_QAM if mod == "qam" else
                              (_lib.CONST_BPSK if mod == "bpsk" else _lib.CONST_GENERIC))
@@ -185,12 +188,22 @@ def test_fuzz_chunked_pipelines(engine, dt, trial):
                          out[0]["num_symbols"], out[0]["num_bits"]), dt, ("ia_iterative", kw), iterative=True)
     if dt == "f64":
         assert np.array_equal(its, [o["runned_iterations"] for o in out]), kw
-    scheme, nt, nr = [("blast", 2, 3), ("blast", 4, 4), ("mrc", 1, 4), ("mrt", 3, 1), ("alamouti", 2, 2)][rs.randint(5)]
+    scheme, nt, nr = FLAT_SCHEMES[rs.randint(5)]
     ns_flat = NS + (NS & 1) if scheme == "alamouti" else NS
     want = _oracle(chains.chain_mimo_scheme, first, count, scheme=scheme, mod=mod, M=M, nt=nt, nr=nr, NSymbs=ns_flat,
                    snr_db=snr)
     _check(*engine.run_mimo_flat(scheme, nt, nr, ns_flat, nv, SEED, first, count, dtype=dt, per_realization=True), want,
            dt, ("flat", scheme, nt, nr, ns_flat))
+    # a second flat draw from the whole list -- SVD / GMD against the canonical-phase oracle included -- with a random MMSE
+    # flag, from a generator of its own so that every other leg keeps its configurations
+    rs_flat = np.random.RandomState(5300 + trial + 1000 * OFFSET)
+    scheme, nt, nr = (FLAT_SCHEMES + [(s, n, n) for s in ("svd", "gmd") for n in (2, 3, 4)])[rs_flat.randint(len(FLAT_SCHEMES) + 6)]
+    mmse = bool(rs_flat.randint(2))
+    ns_flat = NS + (NS & 1) if scheme == "alamouti" else NS
+    want = _oracle(chains.chain_mimo_scheme, first, count, scheme=scheme, mod=mod, M=M, nt=nt, nr=nr, NSymbs=ns_flat,
+                   snr_db=snr, mmse=mmse, canonical=True)
+    _check(*engine.run_mimo_flat(scheme, nt, nr, ns_flat, nv, SEED, first, count, mmse=mmse, dtype=dt, per_realization=True),
+           want, dt, ("flat", scheme, nt, nr, ns_flat, mmse))
     K, r = [(2, 1), (3, 1), (2, 2), (3, 2), (4, 2), (2, 3), (2, 4)][rs.randint(7)]
     # A stream the water-filling switches off is received as exactly 0 (the reference: ~1e-17 of rounding residue):
     # its "decision" is a tie between all points of equal modulus, broken by the last bit of |c_m|, i.e. undefined
