@@ -37,6 +37,11 @@ __host__ __device__ __forceinline__ int pw_slot(int a, int e) { return a * 272 +
 // time index (within the wavefront's 256 samples) held by register c of lane group h after the second DIF pass
 __host__ __device__ __forceinline__ int pw_mtime(int h, int c) { return (c & 3) * 64 + (c >> 2) * 16 + (h & 3) * 4 + (h >> 2); }
 template <int NW> constexpr int pw_lab_stride() { return 16 * NW + 16; }     // bytes per (antenna, group) row: [q + NW u] + bank rotation
+// bytes of the kernel's static LDS arrays (Box-Muller tables, label rows, two records, partial counts, totals): the launcher counts them
+template <int NW> constexpr size_t pw_static_lds() {
+    return (size_t)((kBmLdsDoubles + 1) & ~1) * sizeof(double) + (size_t)64 * pw_lab_stride<NW>() + 2 * (d64_rec<4, 4>() + 1) * sizeof(double2) +
+           64 * sizeof(unsigned) + sizeof(WgTotals);
+}
 
 // Output J of the first radix-NW DIF stage for the sixteen elements k' = g + 16 u of one lane, from the label bytes of its row
 // (byte q + NW u = the label of bin k' + 256 q): Z_u = conj(W_N^(16 J u)) sum_q e^(2 pi i J q / NW) X_q; the lane factor
@@ -171,14 +176,20 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
     constexpr int kLabStride = pw_lab_stride<NW>();
     static_assert(NW == 2 || NW == 4 || NW == 8, "wavefronts per realization");
     extern __shared__ __attribute__((aligned(16))) char pw_smem[];
+    // Round 8: everything of a FIXED size is a static array -- the Box-Muller tables, the label rows, the records, the partial counts, the
+    // totals -- so its address is a compile-time constant and a look-up is its index plus an immediate offset.  Behind the dynamic
+    // block's base (and, before, behind the two constellation tables, whose length is a launch parameter) every table read of the
+    // noise draw paid a vector add of a run-time base.  The dynamic block keeps the planes and the two tables.
+    constexpr int kBm = (kBmLdsDoubles + 1) & ~1;
+    __shared__ __attribute__((aligned(16))) double s_bm[kBm];                          // Box-Muller tables
+    __shared__ __attribute__((aligned(16))) unsigned char s_lab[64 * kLabStride];       // [4][16][kLabStride] labels
+    __shared__ __attribute__((aligned(16))) cx<T> s_rec[2 * (kRec + 1)];                // [2][kRec + 1]
+    __shared__ unsigned s_part[64];                                                     // [2][16][2]
+    __shared__ WgTotals totals;
+    static_assert(sizeof(s_bm) + sizeof(s_lab) + sizeof(s_rec) + sizeof(s_part) + sizeof(totals) == pw_static_lds<NW>(), "launcher's LDS sum");
     T* s_R = reinterpret_cast<T*>(pw_smem);                                  // [NW wavefronts][kPwPlane]: scratch plane of wavefront j
     cx<T>* s_table = reinterpret_cast<cx<T>*>(s_R + NW * kPwPlane);           // [tab_len] constellation
     cx<T>* s_txtab = s_table + ((mp.M + 1) & ~1);                             // [tab_len] constellation x tx scale (TD) / x tx scale N
-    cx<T>* s_rec = s_txtab + ((mp.M + 1) & ~1);                               // [2][kRec + 1]
-    unsigned* s_part = reinterpret_cast<unsigned*>(s_rec + 2 * (kRec + 1));  // [2][16][2]
-    constexpr int kBm = (kBmLdsDoubles + 1) & ~1;
-    double* s_bm = reinterpret_cast<double*>(s_part + 64);                   // [kBm] Box-Muller tables
-    unsigned char* s_lab = reinterpret_cast<unsigned char*>(s_bm + kBm);     // [4][16][kLabStride] labels (16-byte aligned)
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int j = __builtin_amdgcn_readfirstlane(tid >> 6);                 // this wavefront's time class n mod NW (scalar)
@@ -198,12 +209,10 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
         s_txtab[m] = cscale(c, tab_scale);
     }
     bm_tables_to_lds(s_bm, tid, TB);
-    __shared__ WgTotals totals;
     if (tid == 0) wg_zero(totals);
 
     T* s_mine = s_R + j * kPwPlane;
     uint2* s_words_mine = reinterpret_cast<uint2*>(s_mine);                // [16 slots][64 lanes] word pairs of MY samples
-    uint2* s_words_peer = reinterpret_cast<uint2*>(s_R + (j ^ 1) * kPwPlane);  // ... of wavefront j ^ 1's
     uint64_t it = 0, rl_prev = 0;
     cx<T> rec_next = mk<T>(0, 0);
     if (tid < kRec && blockIdx.x < count) rec_next = g_recs[(uint64_t)blockIdx.x * kRec + tid];
@@ -237,8 +246,9 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                     for (int a = 0; a < 4; ++a) dst[a * 16 * kLabStride] = (unsigned char)(w >> (8 * a));
                 }
             }
-            // ---- S0b: the NOISE blocks of half of this lane's sixteen sample pairs: my two words stay, the partner's two go to
-            //      wavefront j ^ 1 (same lane), both through the scratch planes (read back before the channel) ----
+            // ---- S0b: the NOISE blocks of half of this lane's sixteen sample pairs: words 0, 1 are the even sample's (wavefront j & ~1),
+            //      words 2, 3 the odd one's (j | 1), both through the scratch planes (read back before the channel).  Which plane is
+            //      mine is wave-uniform: the two destinations are chosen once, no word pair goes through a select ----
             {
                 const int ln = opaque(lane);
                 const int r = ln >> 4, h = ln & 15;
@@ -246,16 +256,15 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                 // even sample has the flat index i0 = r row + os (N + cp) + cp + NW mtime + (j & ~1): block i0 / 2 = b0 + (NW / 2) pw_mtime(0, cc)
                 const uint64_t i00 = (uint64_t)r * row + (uint64_t)os * (N + cp) + cp + (j & ~1) + 32 * NW * pj + NW * (uint64_t)pw_mtime(h, 0);
                 const uint32_t b0 = (uint32_t)(i00 >> 1);
-                uint2* wm = s_words_mine + (8 * pj) * 64 + ln;
-                uint2* wp = s_words_peer + (8 * pj) * 64 + ln;
+                uint2* w_even = reinterpret_cast<uint2*>(s_R + (j & ~1) * kPwPlane) + (8 * pj) * 64 + ln;
+                uint2* w_odd = reinterpret_cast<uint2*>(s_R + (j | 1) * kPwPlane) + (8 * pj) * 64 + ln;
 #pragma unroll
                 for (int cc = 0; cc < 8; ++cc) {
                     Words4 b;
                     if constexpr (ABL & 128) b.w[0] = b.w[1] = b.w[2] = b.w[3] = b0 + cc;
                     else b = rng.block(STREAM_NOISE, b0 + (uint32_t)(NW / 2) * (uint32_t)pw_mtime(0, cc));
-                    const uint2 even = make_uint2(b.w[0], b.w[1]), odd = make_uint2(b.w[2], b.w[3]);
-                    wm[cc * 64] = pj ? odd : even;
-                    wp[cc * 64] = pj ? even : odd;
+                    w_even[cc * 64] = make_uint2(b.w[0], b.w[1]);
+                    w_odd[cc * 64] = make_uint2(b.w[2], b.w[3]);
                 }
             }
             __syncthreads();                                  // B1: labels and word pairs in place
@@ -496,7 +505,6 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     cx<T> e[4];
-                    int tx[4];
 #pragma unroll
                     for (int jj = 0; jj < 4; ++jj) {
                         const int u = 4 * i + jj;
@@ -505,9 +513,17 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                         xr = __builtin_amdgcn_mfma_f64_4x4x4f64(ngim, v[u].y, xr, 0, 0, 0);
                         xi = __builtin_amdgcn_mfma_f64_4x4x4f64(gre, v[u].y, xi, 0, 0, 0);
                         e[jj] = mk<T>(xr, xi);
-                        tx[jj] = (int)((wds[i] >> (8 * jj)) & 0xFFu);
                     }
-                    walk_decide<DEC, 4>(mp, s_table, nullptr, e, tx, se, be);
+                    if constexpr (DEC == WDEC_SLICER || DEC == WDEC_QAM_CERT) {
+                        // the level-domain count takes the four sent labels as the word they already are (S0a masked every byte):
+                        // no byte is extracted for the decisions
+                        walk_qam_count4<DEC == WDEC_QAM_CERT>(mp, s_table, e, wds[i], se, be);
+                    } else {
+                        int tx[4];
+#pragma unroll
+                        for (int jj = 0; jj < 4; ++jj) tx[jj] = (int)((wds[i] >> (8 * jj)) & 0xFFu);
+                        walk_decide<DEC, 4>(mp, s_table, nullptr, e, tx, se, be);
+                    }
                 }
                 } else {
                     T keep = er[0][0] + ei[NW - 1][UU - 1];
@@ -557,8 +573,8 @@ static int launch_mimo_ofdm_pw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uin
     const int dec = walk_dec_kind(ctx, mp);
     mp.grid.G = 0;
     const size_t tab_len = ((size_t)mp.M + 1) & ~(size_t)1;
-    const size_t lds = (size_t)NW * kPwPlane * sizeof(T) + (2 * tab_len + 2 * (kRec + 1)) * sizeof(cx<T>) + 64 * sizeof(unsigned) +
-                       (size_t)((kBmLdsDoubles + 1) & ~1) * sizeof(double) + (size_t)64 * pw_lab_stride<NW>();
+    const size_t dyn = (size_t)NW * kPwPlane * sizeof(T) + 2 * tab_len * sizeof(cx<T>);      // planes + the two constellation tables
+    const size_t lds = dyn + pw_static_lds<NW>();                                             // + the kernel's static arrays
     MCLE_REQUIRE(lds + 512 <= (size_t)160 * 1024, "part-wave MIMO-OFDM kernel: %zu B of LDS do not fit", lds);
     auto kern = k_run_mimo_ofdm_pw<NW, WDEC_SLICER, WPS, TD, ABL>;
     switch (dec) {
@@ -567,7 +583,7 @@ static int launch_mimo_ofdm_pw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uin
         case WDEC_AXIS4_CERT: kern = k_run_mimo_ofdm_pw<NW, WDEC_AXIS4_CERT, WPS, TD, ABL>; break;
         default: break;
     }
-    MCLE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    MCLE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
     int per_cu = (int)((size_t)160 * 1024 / (lds + 512));
     if (per_cu < 1) per_cu = 1;
     const int by_waves = WPS * 4 / NW;                         // wavefronts per SIMD x four SIMDs / wavefronts per workgroup
@@ -586,7 +602,7 @@ static int launch_mimo_ofdm_pw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uin
         MCLE_LAUNCH_CHECK();
         // (workgroups per resident slot: up to 32 at 1024 points -- 31.36 against 31.53 ms per 2^20 realizations at 16, 31.40 at 48)
         const unsigned grid = (unsigned)oversubscribed_grid(ctx, resident, n, 8, NW == 4 ? 32 : 16);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), lds, ctx->stream, pp, mp, seed, first + off, n, (const cx<T>*)tw,
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), dyn, ctx->stream, pp, mp, seed, first + off, n, (const cx<T>*)tw,
                            (const cx<T>*)recs, d_counters, d_sym ? d_sym + off : nullptr, d_bit ? d_bit + off : nullptr);
         MCLE_LAUNCH_CHECK();
     }
