@@ -722,6 +722,42 @@ typedef struct mcle_bd_cfg {            /* apps/comp_BD/simulate_comp_simple.py:
 int mcle_run_bd(mcle_ctx* ctx, int dtype, const mcle_bd_cfg* cfg, uint64_t seed, uint64_t first,
                 uint64_t count, mcle_counters* d_counters, uint32_t* d_sym_err, uint32_t* d_bit_err);
 
+/* ---- pilot-based channel estimation from CAZAC reference signals (reference_signals/channel_estimation.py:73-131
+ *      CazacBasedChannelEstimator, :135-251 CazacBasedWithOCCChannelEstimator) ----------------------------------
+ * out = FFT_{m ne}( IFFT_{ne}(conj(ref) * y)[0 : num_taps_to_keep + 1] ), times ne when `normalized` (a sequence of unit
+ * norm), m = size_multiplier; note the reference keeps num_taps_to_keep + 1 taps.  y = mean_c(cover[c] * rx[c]) over the
+ * cover-code axis (n_cover = 1 and cover = NULL: no cover code).  d_ref_seq [ne], d_rx [rows][n_cover][ne], d_out
+ * [rows][m ne], complex of `dtype`; cover: HOST pointer, n_cover reals.  A row is one (realization, receive antenna).
+ * Both transforms run as pruned direct DFTs (ne (K + 1)(1 + m) complex FMAs per row), so ne is any size >= 2 with
+ * m ne <= 4096; 0 <= num_taps_to_keep < ne; 1 <= n_cover <= 8.  rows = 0 returns MCLE_OK and launches nothing.
+ * mcle_ctx_last_kernel: "cazac_estimate f64|f32 w<wavefronts per workgroup>" (+ " gtw": table read from global memory). */
+int mcle_cazac_estimate(mcle_ctx* ctx, int dtype, const void* d_ref_seq, int ne, const void* d_rx, size_t rows, int n_cover,
+                        const double* cover, int num_taps_to_keep, int size_multiplier, int normalized, void* d_out);
+
+/* Fused estimation-error Monte Carlo (the experiment of apps/simple_precoded_srs.py without interference cancellation).  One
+ * realization: n_users users send their reference sequences on the same comb; each (user, receive antenna) link is a
+ * block-static tapped delay line h_i = sqrt(p_i) randn_c at integer delays d_i of the m ne-point grid (tap powers
+ * normalised to sum 1), H[k] = sum_i h_i exp(-2 pi j k d_i / (m ne)); received Y[a][n] = sum_u H_u[a][m n] r_u[n] +
+ * sqrt(noise_var) randn_c; every user is estimated as mcle_cazac_estimate does, on chip.  Outputs per realization and
+ * user: d_err [count][n_users] = sum_{a,k} |H^ - H|^2, d_pow [count][n_users] = sum_{a,k} |H|^2 (every entry written; the
+ * caller sums them in index order, so results do not depend on the grid or on how [first, first + count) is split).
+ * Draws: DESIGN section 4 (taps: stream 2, noise: stream 1).  mcle_ctx_last_kernel: "chanest f64|f32 w<n>" (+ " gtw"). */
+typedef struct mcle_chanest_cfg {
+    int32_t ne;                         /* reference sequence length (comb positions), >= 2 */
+    int32_t size_multiplier;            /* m: the channel has m ne subcarriers, m ne <= 4096 */
+    int32_t num_taps_to_keep;           /* K: K + 1 taps are kept, 0 <= K < ne */
+    int32_t n_users, n_rx;              /* <= 8, <= 4 */
+    int32_t n_taps;                     /* <= MCLE_MAX_TAPS */
+    int32_t normalized;                 /* 1: the sequences have unit norm (estimates are multiplied by ne) */
+    int32_t reserved;
+    double noise_var;
+    double tap_power[MCLE_MAX_TAPS];    /* linear, any positive sum (normalised by the library) */
+    int32_t tap_delay[MCLE_MAX_TAPS];   /* 0 <= d < ne */
+    const void* d_ref_seq;              /* DEVICE pointer: the users' sequences [n_users][ne], complex of the call's dtype */
+} mcle_chanest_cfg;
+int mcle_run_chanest(mcle_ctx* ctx, int dtype, const mcle_chanest_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
+                     double* d_err, double* d_pow);
+
 /* ---- same-seed parity mode: NumPy's legacy global RandomState replayed on the device -------
  * Realization r receives exactly what the reference draws after np.random.seed(seed_base + r)
  * (legacy MT19937; util/misc.py:327-355 randn_c = randn real block then imag block, and

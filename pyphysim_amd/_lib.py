@@ -122,6 +122,13 @@ IA_INITS = {"random": 0, "fix": 0, "closed_form": 1, "alt_min": 2, "svd": 3}
 IA_SOLVERS = {"closed_form": 0, "alt_min": 1, "min_leakage": 2, "max_sinr": 3, "mmse": 4}
 
 
+class ChanestCfg(Structure):
+    _fields_ = [("ne", c_int32), ("size_multiplier", c_int32), ("num_taps_to_keep", c_int32), ("n_users", c_int32),
+                ("n_rx", c_int32), ("n_taps", c_int32), ("normalized", c_int32), ("reserved", c_int32),
+                ("noise_var", c_double), ("tap_power", c_double * MAX_TAPS), ("tap_delay", c_int32 * MAX_TAPS),
+                ("d_ref_seq", c_void_p)]
+
+
 class LegacySeg(Structure):
     _fields_ = [("kind", c_int32), ("n", c_int32), ("range", c_uint32), ("reserved", c_uint32)]
 
@@ -222,6 +229,8 @@ _PROTOS = {
     "mcle_block_diagonalize": (c_int, [_P, _P, c_int, c_int, c_double, c_double, c_int, _P, _P, _P, _P, _P, c_size_t]),
     "mcle_pinv": (c_int, [_P, _P, c_int, c_int, c_double, _P, c_size_t]),
     "mcle_run_bd": (c_int, [_P, c_int, POINTER(BdCfg), c_uint64, c_uint64, c_uint64, _P, _P, _P]),
+    "mcle_cazac_estimate": (c_int, [_P, c_int, _P, c_int, _P, c_size_t, c_int, POINTER(c_double), c_int, c_int, c_int, _P]),
+    "mcle_run_chanest": (c_int, [_P, c_int, POINTER(ChanestCfg), c_uint64, c_uint64, c_uint64, _P, _P]),
     "mcle_legacy_draws": (c_int, [_P, POINTER(LegacySeg), c_int, c_uint32, c_uint64, c_uint64, _P, c_size_t, _P,
                                   c_size_t, _P]),
     "mcle_complex_from_parts": (c_int, [_P, c_int, _P, _P, c_double, _P, c_size_t]),

@@ -1101,6 +1101,56 @@ class Engine:
                 cfg.pathloss[i] = float(v)
         return self._run(self.lib.mcle_run_bd, cfg, seed, first, count, dtype, per_realization, counters)
 
+    # ---- pilot-based channel estimation (csrc/kernels_chanest.hip) ------------------------------------
+    def cazac_estimate(self, ref_seq, rx, num_taps_to_keep, size_multiplier=2, normalized=False, cover=None, dtype=None):
+        """CazacBasedChannelEstimator.estimate_channel_freq_domain on rows: ref_seq [ne]; rx [..., ne], or
+        [..., n_cover, ne] with a (real) cover code, whose axis is averaged out first -> [..., size_multiplier * ne]."""
+        dt = self._dt(dtype)
+        d_ref, _ = self._cin(ref_seq, dt)
+        d_rx, host = self._cin(rx, dt)
+        ne = d_ref.size
+        n_cover, c_ptr = 1, None
+        if cover is not None:
+            cov = np.ascontiguousarray(cover, dtype=np.float64).reshape(-1)
+            n_cover, c_ptr = cov.size, cov.ctypes.data_as(ctypes.POINTER(c_double))
+        lead = d_rx.shape[:-1] if cover is None else d_rx.shape[:-2]
+        if d_rx.shape[-1] != ne or (cover is not None and (len(d_rx.shape) < 2 or d_rx.shape[-2] != n_cover)):
+            raise ValueError("rx must be [..., %sne = %d] (got %s)" % ("n_cover = %d, " % n_cover if cover is not None else "",
+                                                                      ne, d_rx.shape))
+        rows = int(np.prod(lead)) if lead else 1
+        out = self.empty(tuple(lead) + (int(size_multiplier) * ne,), _lib.np_complex(dt))
+        self._raise_value(self.lib.mcle_cazac_estimate(self.ctx, dt, d_ref.ptr, ne, d_rx.ptr, rows, n_cover, c_ptr,
+                                                       int(num_taps_to_keep), int(size_multiplier),
+                                                       1 if normalized else 0, out.ptr))
+        return self._out(out, host)
+
+    def run_chanest(self, ref_seqs, n_rx, num_taps_to_keep, size_multiplier, noise_var, tap_power, tap_delay, seed, first,
+                    count, normalized=False, dtype=None, per_realization=False):
+        """Fused estimation-error Monte Carlo (mcle_run_chanest): ref_seqs [n_users, ne] are the users' sequences on one
+        comb, every (user, antenna) link a block-static tapped delay line.  Returns dict(n_realizations, err, pow): per
+        user the sums over the realizations, in index order on the host, of sum_{a,k} |H^ - H|^2 and sum_{a,k} |H|^2;
+        with per_realization=True also the two [count, n_users] arrays."""
+        dt = self._dt(dtype)
+        seqs = np.atleast_2d(np.asarray(ref_seqs))
+        d_seq = self.to_device(seqs, _lib.np_complex(dt))
+        cfg = _lib.ChanestCfg()
+        cfg.ne, cfg.size_multiplier, cfg.num_taps_to_keep = int(seqs.shape[1]), int(size_multiplier), int(num_taps_to_keep)
+        cfg.n_users, cfg.n_rx, cfg.n_taps, cfg.normalized = int(seqs.shape[0]), int(n_rx), len(tap_delay), 1 if normalized else 0
+        cfg.noise_var = float(noise_var)
+        if len(tap_delay) > _lib.MAX_TAPS or len(tap_power) != len(tap_delay):
+            raise ValueError("at most %d taps; powers and delays must match" % _lib.MAX_TAPS)
+        for i, (p, d) in enumerate(zip(tap_power, tap_delay)):
+            cfg.tap_power[i], cfg.tap_delay[i] = float(p), int(d)
+        cfg.d_ref_seq = d_seq.ptr
+        err, pw = self.empty((count, seqs.shape[0]), np.float64), self.empty((count, seqs.shape[0]), np.float64)
+        self._raise_value(self.lib.mcle_run_chanest(self.ctx, dt, byref(cfg), int(seed), int(first), int(count), err.ptr,
+                                                    pw.ptr))
+        e, p = err.get(), pw.get()
+        # (cumsum adds strictly in index order; a plain sum may go pairwise)
+        tot = [np.cumsum(v, axis=0)[-1] if count else np.zeros(seqs.shape[0]) for v in (e, p)]
+        res = {"n_realizations": int(count), "err": tot[0], "pow": tot[1]}
+        return (res, e, p) if per_realization else res
+
     # ---- same-seed parity mode (NumPy legacy RandomState on the device) ----------------------
     def legacy_draws(self, program, seed_base, first, count):
         """program: list of ('randint', n, range) / ('randn', n) / ('rand', n).  Realization r gets

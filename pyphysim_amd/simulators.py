@@ -343,3 +343,64 @@ class IaSimulator(_LinkSimulator):
             its, its_sq = int(c.get("ia_runned_iterations", 0)), int(c.get("ia_runned_iterations_sq", 0))
             res.add_result(Result.from_batch("ia_runned_iterations", Result.RATIOTYPE, its, n, its, its_sq, n))
         return res
+
+
+class ChannelEstimationSimulator(BatchedSimulationRunner):
+    """Estimation-error Monte Carlo of the CAZAC-based channel estimator (the experiment of the reference's
+    apps/simple_precoded_srs.py, without its interference-cancellation variants): `n_users` users send the SRS
+    sequences of one root (cyclic shifts `shifts`) on the same comb of `Ne` positions, every (user, receive antenna)
+    link is a block-static tapped delay line with the given profile (integer delays on the size_multiplier * Ne
+    subcarrier grid), and every user is estimated with `num_taps_to_keep`.  One call into libmcle per batch
+    (Engine.run_chanest).  Results: 'nmse_user{u}' = RATIO(sum |H^ - H|^2, sum |H|^2), 'elapsed_time'."""
+
+    def __init__(self, SNR, n_users=3, shifts=None, Ne=150, size_multiplier=2, num_taps_to_keep=15, Nr=4, root_index=25,
+                 tap_powers_dB=(0.0, -3.0, -6.0, -9.0), tap_delays=(0, 1, 2, 4), rep_max=1000, seed=0, batch_size=4096,
+                 dtype="f32", engine=None, common_random_numbers=False, process_group=None):
+        super().__init__(batch_size=batch_size, process_group=process_group)
+        from .reference_signals import RootSequence, SrsUeSequence
+        self.rep_max = rep_max
+        self.seed = int(seed)
+        self.dtype = dtype
+        self.common_random_numbers = common_random_numbers
+        self._engine = engine
+        shifts = tuple(range(n_users)) if shifts is None else tuple(int(s) for s in shifts)
+        if len(shifts) != n_users or len(set(shifts)) != n_users:
+            raise ValueError("shifts must name one distinct cyclic shift per user")
+        root = RootSequence(root_index=int(root_index), size=int(Ne))
+        self.ref_seqs = np.stack([SrsUeSequence(root, s).seq_array() for s in shifts])
+        self._tap_power = 10.0 ** (np.asarray(tap_powers_dB, dtype=float) / 10.0)
+        self._tap_power = self._tap_power / self._tap_power.sum()
+        self._tap_delay = [int(d) for d in tap_delays]
+        self.EXTRA_KEYS = tuple("%s_user%d" % (k, u) for u in range(n_users) for k in ("err", "pow", "nmse", "nmse_sq"))
+        self.params.add("SNR", np.atleast_1d(np.asarray(SNR, dtype=float)))
+        self.params.set_unpack_parameter("SNR")
+        for k, v in (("n_users", int(n_users)), ("shifts", shifts), ("Ne", int(Ne)), ("size_multiplier", int(size_multiplier)),
+                     ("num_taps_to_keep", int(num_taps_to_keep)), ("Nr", int(Nr)), ("root_index", int(root_index))):
+            self.params.add(k, v)
+
+    engine = _LinkSimulator.engine
+    _seed_for = _LinkSimulator._seed_for
+
+    def _run_batch(self, current_parameters, first_rep, count):
+        p = current_parameters
+        res, err, pw = self.engine.run_chanest(self.ref_seqs, p["Nr"], p["num_taps_to_keep"], p["size_multiplier"],
+                                               1.0 / float(dB2Linear(p["SNR"])), self._tap_power, self._tap_delay,
+                                               self._seed_for(p), first_rep, count, dtype=self.dtype, per_realization=True)
+        c = {k: 0 for k in self.COUNTER_KEYS + ("n_symbols", "n_bits")}
+        c["n_realizations"] = int(count)
+        ratio = np.cumsum(err / pw, axis=0)[-1] if count else np.zeros(p["n_users"])
+        ratio_sq = np.cumsum(np.square(err / pw), axis=0)[-1] if count else np.zeros(p["n_users"])
+        for u in range(p["n_users"]):
+            c["err_user%d" % u], c["pow_user%d" % u] = float(res["err"][u]), float(res["pow"][u])
+            c["nmse_user%d" % u], c["nmse_sq_user%d" % u] = float(ratio[u]), float(ratio_sq[u])
+        return c
+
+    def _results_from_counters(self, current_parameters, c):
+        from .simulations import Result, SimulationResults
+        n = max(int(c["n_realizations"]), 1)
+        res = SimulationResults()
+        for u in range(current_parameters["n_users"]):
+            res.add_result(Result.from_batch("nmse_user%d" % u, Result.RATIOTYPE, float(c.get("err_user%d" % u, 0.0)),
+                                             float(c.get("pow_user%d" % u, 0.0)), float(c.get("nmse_user%d" % u, 0.0)),
+                                             float(c.get("nmse_sq_user%d" % u, 0.0)), n))
+        return res
