@@ -55,9 +55,21 @@ __device__ __forceinline__ void bm_tables_to_lds(double* s_bm, int tid, int nthr
     for (int i = tid; i < kBmThetaLen; i += nthreads) s_bm[kBmLogLen + i] = kBmTheta[i];
     for (int i = tid; i < kBmTrigLen; i += nthreads) s_bm[kBmLogLen + kBmThetaLen + i] = kBmTrig[i];
 }
+// The same tables laid out [kBmLog | kBmTrig | kBmTheta]: kBmLogLen is even, so BOTH pair tables start on a 16-byte boundary of a
+// 16-byte aligned copy and a sample's (1 / c_j, ln c_j) and (cos, sin) are one 16-byte read each (PAIR = true below)
+__device__ __forceinline__ void bm_tables_to_lds_pairs(double* s_bm, int tid, int nthreads) {
+    static_assert(kBmLogLen % 2 == 0, "the trig pairs start on a 16-byte boundary");
+    for (int i = tid; i < kBmLogLen; i += nthreads) s_bm[i] = kBmLog[i];
+    for (int i = tid; i < kBmTrigLen; i += nthreads) s_bm[kBmLogLen + i] = kBmTrig[i];
+    for (int i = tid; i < kBmThetaLen; i += nthreads) s_bm[kBmLogLen + kBmTrigLen + i] = kBmTheta[i];
+}
 #endif
 
+// two neighbours of a pair table as ONE 16-byte load (the table 16-byte aligned: the backend does not merge two 8-byte reads)
+typedef double BmPair __attribute__((vector_size(16)));
+
 // -ln((x0 + 0.5) 2^-32)
+template <bool PAIR = false>
 MCLE_BM_FN double bm_neg_log(uint32_t x0, const double* tlog = kBmLog) {
     const double ud = (double)x0 + 0.5;                                   // exact: u 2^32
     const uint64_t bits = __builtin_bit_cast(uint64_t, ud);
@@ -69,7 +81,15 @@ MCLE_BM_FN double bm_neg_log(uint32_t x0, const double* tlog = kBmLog) {
     const double m = __builtin_bit_cast(double, ((uint64_t)(ebase | mant) << 32) | (uint64_t)(uint32_t)bits);
     const double c = __builtin_bit_cast(double, (uint64_t)(ebase + (j << 14)) << 32);    // (1 + j/64) [/ 2]; j = 64 -> 1
     const int e = (int)(hi >> 20) - (1023 + 32) + (fold ? 1 : 0);
-    const double inv_c = tlog[2 * j], lnc = tlog[2 * j + 1];
+    double inv_c, lnc;
+    if constexpr (PAIR) {
+        const BmPair t = *reinterpret_cast<const BmPair*>(tlog + 2 * j);
+        inv_c = t[0];
+        lnc = t[1];
+    } else {
+        inv_c = tlog[2 * j];
+        lnc = tlog[2 * j + 1];
+    }
     const double r = (m - c) * inv_c;
     const double r2 = r * r;
     // log1p(r) = r + r^2 (-1/2 + r/3 + r^2 ((-1/4 + r/5) + r^2 (-1/6 + r/7)))
@@ -96,10 +116,19 @@ MCLE_BM_FN double bm_sqrt(double a) {
 }
 
 // cos / sin of the double fl(2 pi_d * x1 2^-32)
+template <bool PAIR = false>
 MCLE_BM_FN void bm_sincos(uint32_t x1, double& c, double& s, const double* ttheta = kBmTheta, const double* ttrig = kBmTrig) {
     const double ang = (double)x1 * 0x1.921fb54442d18p-30;                // (2 pi_d) 2^-32: fl(.) == NumPy's 2.0*np.pi*(x1*2**-32)
     const uint32_t k = ((x1 >> 24) + 1u) >> 1;                            // nearest node, 0 .. 128
-    const double ct = ttrig[2 * k], st = ttrig[2 * k + 1];
+    double ct, st;
+    if constexpr (PAIR) {
+        const BmPair t = *reinterpret_cast<const BmPair*>(ttrig + 2 * k);
+        ct = t[0];
+        st = t[1];
+    } else {
+        ct = ttrig[2 * k];
+        st = ttrig[2 * k + 1];
+    }
     const double r = ang - ttheta[k];                                     // exact
     const double s2 = r * r;
     double p = MCLE_BM_FMA(s2, -1.0 / 5040.0, 1.0 / 120.0);

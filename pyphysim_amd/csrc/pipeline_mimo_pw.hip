@@ -27,6 +27,10 @@
 // Round 7: the text above is the TIME-DOMAIN form (template parameter TD = true, option f64_threads = 265).  The default form leaves the
 // transmit side out -- the channel is flat, so only the noise is transformed and H X joins its spectrum in front of the decode: see the
 // comment at k_run_mimo_ofdm_pw.
+// Round 10: the default form deals the 4 NW (antenna, time class) partial transforms BY LANE ROW (template parameter ROWS = true): lane
+// row rho of wavefront w owns the pair f = NW antenna + class = 4 w + rho, so the two samples of a Philox NOISE block sit sixteen lanes
+// apart in ONE wavefront and their words change rows in registers -- no LDS round trip, no barrier B1.  The map of
+// the text above (wavefront = class, row = antenna) stays as ROWS = false, option f64_threads = 266: the A/B partner.
 #include "mimo_planar_common.hpp"
 #include "walk_f64.hpp"
 
@@ -41,6 +45,22 @@ template <int NW> constexpr int pw_lab_stride() { return 16 * NW + 16; }     // 
 template <int NW> constexpr size_t pw_static_lds() {
     return (size_t)((kBmLdsDoubles + 1) & ~1) * sizeof(double) + (size_t)64 * pw_lab_stride<NW>() + 2 * (d64_rec<4, 4>() + 1) * sizeof(double2) +
            64 * sizeof(unsigned) + sizeof(WgTotals);
+}
+
+// x of the odd lane rows (16-31, 48-63) changes places with y of the even rows sixteen lanes below: v_permlane16_swap_b32
+__device__ __forceinline__ void pw_row_swap(uint32_t& x, uint32_t& y) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#if __has_builtin(__builtin_amdgcn_permlane16_swap)
+    const auto s = __builtin_amdgcn_permlane16_swap(x, y, false, false);
+    x = s[0];
+    y = s[1];
+#else
+    const bool odd = (__lane_id() & 16) != 0;
+    const uint32_t give = odd ? x : y, got = (uint32_t)__shfl_xor((int)give, 16);
+    if (odd) x = got;
+    else y = got;
+#endif
+#endif
 }
 
 // Output J of the first radix-NW DIF stage for the sixteen elements k' = g + 16 u of one lane, from the label bytes of its row
@@ -166,7 +186,17 @@ __device__ __forceinline__ void pw_first_stage(const unsigned char* lab_row, con
 // ABL (MCLE_EXPERIMENTS builds only, option f64_variant: WRONG results by construction): 32 = no label draws / look-ups,
 // 64 = no transmit passes (TD only: the default form has none, the bit switches nothing off there), 128 = no noise draws,
 // 256 = no channel products (TD) / no signal contraction (default form), 512 = no receive passes, 1024 = no decode
-template <int NW, int DEC, int WPS, bool TD = false, int ABL = 0>
+// ROWS = true (the default form's default since round 10): OWNERSHIP BY LANE ROW.  The receive passes and the transposition work per
+// lane row and do not care which (antenna, class) pair a row carries, so the 4 NW pairs, flattened f = NW antenna + class, are dealt
+// f = 4 w + rho to lane row rho = lane >> 4 of wavefront w (NW = 4: wavefront = antenna, row = class).  Even and odd classes are then
+// even and odd rows of one wavefront: every lane draws eight NOISE blocks -- an even row those of registers cc < 8, its partner lane
+// + 16 those of registers 8 + cc -- and two row swaps per block leave (w0, w1) = the words of register cc and (w2, w3) = those of
+// register 8 + cc in EVERY lane: static register indices, no select, no LDS.  With the words gone nothing is published before B2 (the
+// labels of S0a are first read behind B4): barrier B1 is not issued.  Wavefront w leaves the partial spectrum of its row rho in slice
+// f of the planes (272 doubles each, + 16 for an odd antenna: the rows r, r + 1 of one reading half-wave land on the two halves of
+// the bank row); the reader of antenna r takes class jj from slice NW r + jj.  Every floating-point operation and its operands are
+// those of ROWS = false (option f64_threads = 266) -- only the wavefront and the lane where it runs moved.
+template <int NW, int DEC, int WPS, bool TD = false, int ABL = 0, bool ROWS = !TD>
 __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp, ModemParams<double> mp, uint64_t seed, uint64_t first,
                                                                    uint64_t count, const double2* __restrict__ g_tw,
                                                                    const double2* __restrict__ g_recs, mcle_counters* counters,
@@ -175,6 +205,8 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
     constexpr int N = 256 * NW, NT = 4, NR = 4, kRec = d64_rec<NT, NR>(), TB = 64 * NW, UU = 16 / NW;
     constexpr int kLabStride = pw_lab_stride<NW>();
     static_assert(NW == 2 || NW == 4 || NW == 8, "wavefronts per realization");
+    static_assert(!(TD && ROWS), "the time-domain form keeps the map wavefront = class");
+    constexpr int kLogNW = NW == 2 ? 1 : NW == 4 ? 2 : 3;
     extern __shared__ __attribute__((aligned(16))) char pw_smem[];
     // Round 8: everything of a FIXED size is a static array -- the Box-Muller tables, the label rows, the records, the partial counts, the
     // totals -- so its address is a compile-time constant and a look-up is its index plus an immediate offset.  Behind the dynamic
@@ -208,7 +240,8 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
         s_table[m] = c;
         s_txtab[m] = cscale(c, tab_scale);
     }
-    bm_tables_to_lds(s_bm, tid, TB);
+    if constexpr (ROWS) bm_tables_to_lds_pairs(s_bm, tid, TB);        // (same size: the pair tables first, each pair one 16-byte read)
+    else bm_tables_to_lds(s_bm, tid, TB);
     if (tid == 0) wg_zero(totals);
 
     T* s_mine = s_R + j * kPwPlane;
@@ -249,7 +282,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
             // ---- S0b: the NOISE blocks of half of this lane's sixteen sample pairs: words 0, 1 are the even sample's (wavefront j & ~1),
             //      words 2, 3 the odd one's (j | 1), both through the scratch planes (read back before the channel).  Which plane is
             //      mine is wave-uniform: the two destinations are chosen once, no word pair goes through a select ----
-            {
+            if constexpr (!ROWS) {
                 const int ln = opaque(lane);
                 const int r = ln >> 4, h = ln & 15;
                 // register c = 8 pj + cc holds sample time n = NW pw_mtime(h, c) + j, pw_mtime(h, c) = pw_mtime(h, cc) + 32 pj; the pair's
@@ -267,16 +300,22 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                     w_odd[cc * 64] = make_uint2(b.w[2], b.w[3]);
                 }
             }
-            __syncthreads();                                  // B1: labels and word pairs in place
-            if (tid == 0 && os == 0 && it > 0) {              // every wave is past the previous realization: account it
-                const unsigned* qq = s_part + (buf ^ 1) * 32;
-                unsigned ts = 0, tb = 0;
+            // every wave is past the previous realization: account it (ROWS: behind B2, the first barrier of the symbol)
+            auto account_prev = [&]() {
+                if (tid == 0 && os == 0 && it > 0) {
+                    const unsigned* qq = s_part + (buf ^ 1) * 32;
+                    unsigned ts = 0, tb = 0;
 #pragma unroll
-                for (int i = 0; i < NW; ++i) {
-                    ts += qq[2 * i];
-                    tb += qq[2 * i + 1];
+                    for (int i = 0; i < NW; ++i) {
+                        ts += qq[2 * i];
+                        tb += qq[2 * i + 1];
+                    }
+                    wg_account(totals, ts, tb, s_rec[(buf ^ 1) * (kRec + 1) + 2 * NT * NR].x != 0.0, rl_prev, sym_out, bit_out);
                 }
-                wg_account(totals, ts, tb, s_rec[(buf ^ 1) * (kRec + 1) + 2 * NT * NR].x != 0.0, rl_prev, sym_out, bit_out);
+            };
+            if constexpr (!ROWS) {
+                __syncthreads();                              // B1: labels and word pairs in place
+                account_prev();
             }
             cx<T> v[16];
             // ---- S1: lane (a, g): the first-stage output of this wavefront's time class for k' = g + 16 u; compiled per class ----
@@ -322,7 +361,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
             }
             // ---- the word pairs of my sixteen noise samples (before the scratch plane is reused) ----
             uint2 nw[16];
-            {
+            if constexpr (!ROWS) {
                 const int ln = opaque(lane);
 #pragma unroll
                 for (int c = 0; c < 16; ++c) nw[c] = s_words_mine[c * 64 + ln];
@@ -351,11 +390,37 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                 r16_pass<T, true, false, 0, false, true, true, false, true>(nullptr, nullptr, 0, none, nullptr, 0, v, v);
             }
             // ---- default form: the noise alone, lane (r, h), register c = sample NW pw_mtime(h, c) + j of receive antenna r ----
-            if constexpr (!TD) {
+            if constexpr (!TD && !ROWS) {
 #pragma unroll
                 for (int c = 0; c < 16; ++c) {
                     if constexpr (ABL & 128) v[c] = mk<T>((T)nw[c].x, sigma);
                     else v[c] = cn_words(nw[c].x, nw[c].y, sigma, s_bm);
+                }
+            }
+            // ---- ROWS: lane (rho, h) of wavefront j, register c = sample NW pw_mtime(h, c) + class of the pair f = 4 j + rho.  The
+            //      block of registers (cc, 8 + cc) of an even row is drawn by the row itself (cc) and by the row above (8 + cc:
+            //      pw_mtime(h, 8 + cc) = pw_mtime(h, cc) + 32); its flat sample index is i0 = antenna row + os (N + cp) + cp +
+            //      NW mtime + (class & ~1), block i0 / 2 as in S0b ----
+            if constexpr (ROWS) {
+                const int ln = opaque(lane);
+                const int rho = ln >> 4, h = ln & 15;
+                const int f = 4 * j + rho, ant = f >> kLogNW, cls = f & (NW - 1);
+                const uint64_t i00 = (uint64_t)ant * row + (uint64_t)os * (N + cp) + cp + (cls & ~1) + 32 * NW * (rho & 1) + NW * (uint64_t)pw_mtime(h, 0);
+                const uint32_t b0 = (uint32_t)(i00 >> 1);
+#pragma unroll
+                for (int cc = 0; cc < 8; ++cc) {
+                    Words4 b;
+                    if constexpr (ABL & 128) b.w[0] = b.w[1] = b.w[2] = b.w[3] = b0 + cc;
+                    else b = rng.block(STREAM_NOISE, b0 + (uint32_t)(NW / 2) * (uint32_t)pw_mtime(0, cc));
+                    pw_row_swap(b.w[0], b.w[2]);
+                    pw_row_swap(b.w[1], b.w[3]);
+                    if constexpr (ABL & 128) {
+                        v[cc] = mk<T>((T)b.w[0], sigma);
+                        v[8 + cc] = mk<T>((T)b.w[2], sigma);
+                    } else {
+                        v[cc] = cn_from_words_lds_pairs(b.w[0], b.w[1], sigma, s_bm);
+                        v[8 + cc] = cn_from_words_lds_pairs(b.w[2], b.w[3], sigma, s_bm);
+                    }
                 }
             }
             // ---- channel: R_r = sum_a H[r][a] T_a + noise on v_mfma_f64_4x4x4 (pipeline_mimo_qw.hip: the lane maps) ----
@@ -417,15 +482,20 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
             {
                 const int ln = opaque(lane);
                 const int r = ln >> 4, g = ln & 15;
-                const int wpos = r * 272 + g, rpos = r * 272 + g + 16 * UU * j;
+                // ROWS: my row r carries the pair f = 4 j + r -> slice f = row r of my plane, + 16 for an odd antenna; antenna r's
+                // class jj is slice NW r + jj
+                constexpr int kClass = ROWS ? 272 : kPwPlane;  // doubles from class jj to class jj + 1 of one antenna
+                const int wpos = r * 272 + g + (ROWS ? 16 * (((4 * j + r) >> kLogNW) & 1) : 0);
+                const int rpos = (ROWS ? NW * r * 272 + 16 * (r & 1) : r * 272) + g + 16 * UU * j;
                 r16_wave_sync();                               // (my own reads of the transposition are done)
 #pragma unroll
                 for (int u = 0; u < 16; ++u) s_mine[wpos + 16 * u] = v[u].x;
                 __syncthreads();                               // B2
+                if constexpr (ROWS) account_prev();
 #pragma unroll
                 for (int jj = 0; jj < NW; ++jj)
 #pragma unroll
-                    for (int uu = 0; uu < UU; ++uu) er[jj][uu] = s_R[jj * kPwPlane + rpos + 16 * uu];
+                    for (int uu = 0; uu < UU; ++uu) er[jj][uu] = s_R[jj * kClass + rpos + 16 * uu];
                 __syncthreads();                               // B3
 #pragma unroll
                 for (int u = 0; u < 16; ++u) s_mine[wpos + 16 * u] = v[u].y;
@@ -433,7 +503,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
 #pragma unroll
                 for (int jj = 0; jj < NW; ++jj)
 #pragma unroll
-                    for (int uu = 0; uu < UU; ++uu) ei[jj][uu] = s_R[jj * kPwPlane + rpos + 16 * uu];
+                    for (int uu = 0; uu < UU; ++uu) ei[jj][uu] = s_R[jj * kClass + rpos + 16 * uu];
             }
             // ---- last radix-NW stage for my UU elements (register q + NW uu = bin k' + 256 q), [default form: the signal,] decode on
             //      the matrix cores, decisions ----
@@ -560,7 +630,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
     }
 }
 
-template <int NW, int WPS, bool TD = false, int ABL = 0>
+template <int NW, int WPS, bool TD = false, int ABL = 0, bool ROWS = !TD>
 static int launch_mimo_ofdm_pw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
                                mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit) {
     using T = double;
@@ -576,11 +646,11 @@ static int launch_mimo_ofdm_pw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uin
     const size_t dyn = (size_t)NW * kPwPlane * sizeof(T) + 2 * tab_len * sizeof(cx<T>);      // planes + the two constellation tables
     const size_t lds = dyn + pw_static_lds<NW>();                                             // + the kernel's static arrays
     MCLE_REQUIRE(lds + 512 <= (size_t)160 * 1024, "part-wave MIMO-OFDM kernel: %zu B of LDS do not fit", lds);
-    auto kern = k_run_mimo_ofdm_pw<NW, WDEC_SLICER, WPS, TD, ABL>;
+    auto kern = k_run_mimo_ofdm_pw<NW, WDEC_SLICER, WPS, TD, ABL, ROWS>;
     switch (dec) {
-        case WDEC_QAM_CERT: kern = k_run_mimo_ofdm_pw<NW, WDEC_QAM_CERT, WPS, TD, ABL>; break;
-        case WDEC_QUAD_CERT: kern = k_run_mimo_ofdm_pw<NW, WDEC_QUAD_CERT, WPS, TD, ABL>; break;
-        case WDEC_AXIS4_CERT: kern = k_run_mimo_ofdm_pw<NW, WDEC_AXIS4_CERT, WPS, TD, ABL>; break;
+        case WDEC_QAM_CERT: kern = k_run_mimo_ofdm_pw<NW, WDEC_QAM_CERT, WPS, TD, ABL, ROWS>; break;
+        case WDEC_QUAD_CERT: kern = k_run_mimo_ofdm_pw<NW, WDEC_QUAD_CERT, WPS, TD, ABL, ROWS>; break;
+        case WDEC_AXIS4_CERT: kern = k_run_mimo_ofdm_pw<NW, WDEC_AXIS4_CERT, WPS, TD, ABL, ROWS>; break;
         default: break;
     }
     MCLE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
@@ -589,8 +659,9 @@ static int launch_mimo_ofdm_pw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uin
     const int by_waves = WPS * 4 / NW;                         // wavefronts per SIMD x four SIMDs / wavefronts per workgroup
     if (per_cu > by_waves) per_cu = by_waves;
     const uint64_t resident = (uint64_t)ctx->n_cu * per_cu;
-    // which form served the call (mcle_ctx_last_kernel); "/w2": the two-wavefront register bound where three is the default (NW = 2, 4)
-    ctx->set_kernel("mimo_ofdm_pw<%d>/%s%s", NW, TD ? "time" : "freq", WPS == (NW == 8 ? 2 : 3) ? "" : "/w2");
+    // which form served the call (mcle_ctx_last_kernel); "/w2": the two-wavefront register bound where three is the default (NW = 2, 4);
+    // "/a": the default form with the ownership map of rounds 6 - 9 (wavefront = class, row = antenna)
+    ctx->set_kernel("mimo_ofdm_pw<%d>/%s%s%s", NW, TD ? "time" : "freq", WPS == (NW == 8 ? 2 : 3) ? "" : "/w2", !TD && !ROWS ? "/a" : "");
     const uint64_t kSlice = 1ull << 20;          // realizations per record kernel + link kernel pair (553 MB of records; 2^18: three more tails per bench step, -0.6 %)
     const uint64_t slice = count < kSlice ? count : kSlice;
     void* recs = nullptr;
@@ -620,10 +691,16 @@ int run_mimo_ofdm_pw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed
         ModemParams<double> mp = pipe_modem<double>(ctx, cfg->demod_method);
         if (walk_dec_kind(ctx, mp) == WDEC_GENERIC) return MCLE_E_UNSUPPORTED;     // no certificate: the planar kernel's candidate grid
     }
-    // MCLE_OPT_F64_THREADS: 265 = the time-domain form (three wavefronts per SIMD); 262 / 264 = two wavefronts per SIMD; the
-    // ablations of the MCLE_EXPERIMENTS builds (option f64_variant) apply to whichever form the option selects
+    // MCLE_OPT_F64_THREADS: 265 = the time-domain form (three wavefronts per SIMD); 262 / 264 = two wavefronts per SIMD; 266 = the
+    // default form with the ownership map of rounds 6 - 9 (noise words through LDS, barrier B1); the ablations of the
+    // MCLE_EXPERIMENTS builds (option f64_variant) apply to the time-domain form and to the default form with its default map
     const bool two = ctx->opt[MCLE_OPT_F64_THREADS] == 262 || ctx->opt[MCLE_OPT_F64_THREADS] == 264;
     const bool td = ctx->opt[MCLE_OPT_F64_THREADS] == 265;
+    if (ctx->opt[MCLE_OPT_F64_THREADS] == 266) {
+        if (cfg->fft_size == 2048) return launch_mimo_ofdm_pw<8, 2, false, 0, false>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
+        if (cfg->fft_size == 512) return launch_mimo_ofdm_pw<2, 3, false, 0, false>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
+        return launch_mimo_ofdm_pw<4, 3, false, 0, false>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
+    }
     if (cfg->fft_size == 2048) {     // eight wavefronts = 512 threads: one workgroup per CU (86 KiB of LDS), two wavefronts per SIMD
         return td ? launch_mimo_ofdm_pw<8, 2, true>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit)
                   : launch_mimo_ofdm_pw<8, 2>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
