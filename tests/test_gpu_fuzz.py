@@ -1,7 +1,8 @@
 """GPU: seeded random configurations of every fused pipeline against the oracle chains under common random
 numbers (mcle-philox-v1).  The f64 instantiation must reproduce the oracle's per-realization symbol and bit
 error counts exactly, whatever the modulation, the sizes, the SNR or the position of the realization range;
-the f32 instantiation stays within the north-star tolerance on the same draws."""
+the f32 instantiation stays within the north-star tolerance on the same draws.  The estimation-error pipeline has no
+counts: its per-realization error sums stay within the operator tolerance of the restatement's (test_fuzz_chanest)."""
 import numpy as np
 import pytest
 
@@ -215,6 +216,39 @@ def test_fuzz_chunked_pipelines(engine, dt, trial):
     want = _oracle(chains.chain_bd, first, count, canonical=True, **kw)
     _check(*engine.run_bd(K, r, NS, kw["iPu"], nv, SEED, first, count, bd_noise_var=kw["bd_noise_var"],
                           waterfilling=kw["waterfill"], dtype=dt, per_realization=True), want, dt, ("bd", kw))
+
+
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+@pytest.mark.parametrize("trial", range(N_TRIALS))
+def test_fuzz_chanest(engine, dt, trial):
+    """The estimation-error pipeline (csrc/kernels_chanest.hip) on random sizes, size multipliers, kept taps, users, antennas,
+    delay profiles, noise levels and realization offsets, against the NumPy restatement on the same draws.  The sequences are
+    unit-modulus random phases (the kernel does not need them to be CAZAC).  Bound: an estimate within the operator tolerance
+    (tests/test_gpu_chanest.py), relative to ||H||, of the restatement's."""
+    import chanest_oracle as co
+    rs = np.random.RandomState(1100 + trial + 1000 * OFFSET)
+    ne = int(rs.randint(2, 513))
+    m = int(rs.randint(1, min(4, 4096 // ne) + 1))
+    K = int(rs.randint(0, ne))
+    n_users, n_rx, n_taps = int(rs.randint(1, 9)), int(rs.randint(1, 5)), int(rs.randint(1, min(24, ne) + 1))
+    delay = sorted(rs.choice(ne, size=n_taps, replace=False).tolist())
+    power = rs.uniform(0.1, 1.1, size=n_taps).tolist()
+    nv = float(10.0 ** rs.uniform(-3, 0))
+    first, count = int(rs.randint(0, 1 << 40)), 6
+    seqs = np.exp(2j * np.pi * rs.rand(n_users, ne))
+    cfg = dict(ref_seqs=seqs, n_rx=n_rx, size_multiplier=m, num_taps_to_keep=K, noise_var=nv, tap_power=power, tap_delay=delay)
+    what = ("chanest", dt, dict(ne=ne, m=m, K=K, n_users=n_users, n_rx=n_rx, tap_delay=delay, tap_power=power, noise_var=nv,
+                                first=first, count=count))
+    res, err, pw = engine.run_chanest(seqs, n_rx, K, m, nv, power, delay, SEED, first, count, dtype=dt, per_realization=True)
+    assert engine.last_kernel().startswith("chanest " + dt), what
+    want = [co.chanest_realization(SEED, r, cfg) for r in range(first, first + count)]
+    want_err, want_pow = np.array([w[0] for w in want]), np.array([w[1] for w in want])
+    tol = 1e-11 if dt == "f64" else 2e-5
+    r_err = float(np.max(np.abs(err - want_err) / (2 * tol * np.sqrt(want_err * want_pow) + tol ** 2 * want_pow)))
+    r_pow = float(np.max(np.abs(pw - want_pow) / (2 * tol * want_pow)))
+    print("chanest %s trial %d: worst ratio to the bound err %.3g pow %.3g %s" % (dt, trial, r_err, r_pow, engine.last_kernel()))
+    assert err.shape == (count, n_users) and res["n_realizations"] == count, what
+    assert r_err <= 1.0 and r_pow <= 1.0, (what, r_err, r_pow)
 
 
 N_MFMA_TRIALS = int(os.environ.get("MCLE_FUZZ_TRIALS", "10"))
