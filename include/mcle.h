@@ -764,6 +764,38 @@ typedef struct mcle_chanest_cfg {
 int mcle_run_chanest(mcle_ctx* ctx, int dtype, const mcle_chanest_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
                      double* d_err, double* d_pow);
 
+/* The staged cancellation operator: out[row][n] = rx[row][n] - est[row][m n] * ref[n], m = size_multiplier -- the contribution
+ * of an estimated user taken out of the comb it was estimated from.  d_ref_seq [ne], d_rx and d_out [rows][ne], d_est
+ * [rows][m ne] as mcle_cazac_estimate writes it, complex of `dtype`; d_out may be d_rx (in place).  ne >= 2, m >= 1,
+ * m ne <= 4096.  rows = 0 returns MCLE_OK and launches nothing.  mcle_ctx_last_kernel: "cazac_cancel f64|f32". */
+int mcle_cazac_cancel(mcle_ctx* ctx, int dtype, const void* d_ref_seq, int ne, const void* d_rx, const void* d_est, size_t rows,
+                      int size_multiplier, void* d_out);
+
+/* mcle_run_chanest with a path loss per user and interference cancellation at the one receiver (the experiment of
+ * apps/simple_precoded_srs.py:127-345).  Same draws; the taps of every link of user u are multiplied by sqrt(link_gain[u]),
+ * and the true response H_u (hence d_pow) includes the gain.  With k = m n the comb bins:
+ *   mode 0: every user is estimated from the received comb Y, as mcle_run_chanest does.
+ *   mode 1: the direct user d is estimated from Y; R0[a][n] = Y[a][n] - H^_d[a][m n] r_d[n]; every other user from R0.
+ *   mode 2: mode 1, then an ordered successive cancellation over the others: they are ordered by the Frobenius norm of
+ *           their first estimates over all antennas and all m ne bins, descending (an exact tie: the higher user index
+ *           counts as stronger); the strongest keeps its first estimate, and for s = 2, 3, ... the s-th strongest is
+ *           estimated again from R_{s-1} = R_{s-2} - H^_o[m n] r_o[n], o the (s-1)-th strongest with its final estimate.
+ * d_err, d_pow [count][n_users] as mcle_run_chanest; d_order (int32 [count][n_users], may be NULL): the order in which the
+ * users received their final estimates, the direct user first, then the others by descending norm (mode 2) or ascending
+ * index (mode 1); in mode 0 the row is 0, 1, 2, ... .  Every rule of mcle_run_chanest applies to `base`; mode in {0, 1, 2},
+ * 0 <= direct_user < n_users, link_gain[u] > 0 and finite for u < n_users.  count = 0 returns MCLE_OK and launches
+ * nothing.  The output arrays do not depend on the grid, on MCLE_OPT_GRID_OVERSUB or on how [first, first + count) is split.
+ * A shape whose one realization does not fit the 160 KiB of LDS is refused ("does not fit").
+ * mcle_ctx_last_kernel: "chanest_ic f64|f32 w<n>" (+ " gtw"). */
+typedef struct mcle_chanest_ic_cfg {
+    mcle_chanest_cfg base;
+    int32_t mode;                       /* 0: none, 1: direct link removed, 2: direct link removed + ordered SIC */
+    int32_t direct_user;                /* the receiver's own user */
+    double link_gain[8];                /* linear power gain per user, > 0 */
+} mcle_chanest_ic_cfg;
+int mcle_run_chanest_ic(mcle_ctx* ctx, int dtype, const mcle_chanest_ic_cfg* cfg, uint64_t seed, uint64_t first,
+                        uint64_t count, double* d_err, double* d_pow, int32_t* d_order);
+
 /* ---- same-seed parity mode: NumPy's legacy global RandomState replayed on the device -------
  * Realization r receives exactly what the reference draws after np.random.seed(seed_base + r)
  * (legacy MT19937; util/misc.py:327-355 randn_c = randn real block then imag block, and

@@ -129,6 +129,13 @@ class ChanestCfg(Structure):
                 ("d_ref_seq", c_void_p)]
 
 
+class ChanestIcCfg(Structure):
+    _fields_ = [("base", ChanestCfg), ("mode", c_int32), ("direct_user", c_int32), ("link_gain", c_double * 8)]
+
+
+CHANEST_IC_MODES = {"none": 0, "direct": 1, "sic": 2}
+
+
 class LegacySeg(Structure):
     _fields_ = [("kind", c_int32), ("n", c_int32), ("range", c_uint32), ("reserved", c_uint32)]
 
@@ -231,6 +238,8 @@ _PROTOS = {
     "mcle_run_bd": (c_int, [_P, c_int, POINTER(BdCfg), c_uint64, c_uint64, c_uint64, _P, _P, _P]),
     "mcle_cazac_estimate": (c_int, [_P, c_int, _P, c_int, _P, c_size_t, c_int, POINTER(c_double), c_int, c_int, c_int, _P]),
     "mcle_run_chanest": (c_int, [_P, c_int, POINTER(ChanestCfg), c_uint64, c_uint64, c_uint64, _P, _P]),
+    "mcle_cazac_cancel": (c_int, [_P, c_int, _P, c_int, _P, _P, c_size_t, c_int, _P]),
+    "mcle_run_chanest_ic": (c_int, [_P, c_int, POINTER(ChanestIcCfg), c_uint64, c_uint64, c_uint64, _P, _P, _P]),
     "mcle_legacy_draws": (c_int, [_P, POINTER(LegacySeg), c_int, c_uint32, c_uint64, c_uint64, _P, c_size_t, _P,
                                   c_size_t, _P]),
     "mcle_complex_from_parts": (c_int, [_P, c_int, _P, _P, c_double, _P, c_size_t]),

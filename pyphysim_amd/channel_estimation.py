@@ -9,13 +9,18 @@ leading batch axis of realizations.  Everything goes through ONE kernel launch p
 
 times Ne when the sequence has unit norm.  NumPy in, NumPy out; a
 :class:`pyphysim_amd.engine.DeviceArray` stays on the device.
+
+:func:`estimate_with_interference_cancellation` is the staged form of the reference's apps/simple_precoded_srs.py rules
+(direct-link removal, ordered successive cancellation) for a received signal the caller brings: ``mcle_cazac_estimate`` and
+``mcle_cazac_cancel`` launches with the ordering done on the host.  The fused Monte Carlo is ``Engine.run_chanest_ic``.
 """
 import numpy as np
 
+from . import _lib
 from .engine import DeviceArray, get_engine
 from .reference_signals import UeSequence
 
-__all__ = ["CazacBasedChannelEstimator", "CazacBasedWithOCCChannelEstimator"]
+__all__ = ["CazacBasedChannelEstimator", "CazacBasedWithOCCChannelEstimator", "estimate_with_interference_cancellation"]
 
 
 def _as_array(x):
@@ -92,3 +97,52 @@ class CazacBasedWithOCCChannelEstimator(CazacBasedChannelEstimator):
         if not extra_dimension:
             rx = rx.reshape(tuple(rx.shape[:-1]) + (nc, rx.shape[-1] // nc))
         return self._launch(rx, num_taps_to_keep, cover=np.real(self._cover))
+
+
+def estimate_with_interference_cancellation(ref_seqs, rx, num_taps_to_keep, size_multiplier, direct_user, mode, engine=None,
+                                            dtype=None):
+    """Estimates of every user on one comb at the receiver of `direct_user`, with interference cancellation.
+
+    ref_seqs [n_users, Ne]; rx [..., Nr, Ne] (NumPy): the received comb of Nr antennas per realization.  mode 0 / 'none':
+    every user from rx; 1 / 'direct': the direct user is estimated from rx and its contribution est[::m] * ref subtracted,
+    the others are estimated from that residual; 2 / 'sic': then the others are ordered by the norm of their first estimates
+    over the antennas and subcarriers, descending (a tie: the higher index first), and each one after the strongest is
+    estimated again from the residual left by the final estimates of all stronger ones.  Returns [..., Nr, n_users, m Ne]:
+    rx's leading axes, then the user, then the subcarrier.
+    The order is decided per realization on the host; realizations that share an order share their launches."""
+    mode = int(_lib.CHANEST_IC_MODES.get(mode, mode))
+    seqs = np.atleast_2d(np.asarray(ref_seqs))
+    n_users, ne = seqs.shape
+    rx = np.asarray(rx)
+    if mode not in (0, 1, 2) or not 0 <= int(direct_user) < n_users:
+        raise ValueError("mode must be 0, 1 or 2 and direct_user one of the %d users" % n_users)
+    if rx.ndim < 2 or rx.shape[-1] != ne:
+        raise ValueError("rx must be [..., Nr, Ne = %d] (got %s)" % (ne, rx.shape))
+    lead, nr, m, d = rx.shape[:-2], rx.shape[-2], int(size_multiplier), int(direct_user)
+    eng = get_engine() if engine is None else engine
+    y = rx.reshape((-1, nr, ne))
+
+    def estimate(u, rows):
+        return eng.cazac_estimate(seqs[u], rows, num_taps_to_keep, size_multiplier=m, dtype=dtype)
+
+    first = d if mode else 0
+    est = [None] * n_users
+    est[first] = estimate(first, y)
+    others = [u for u in range(n_users) if u != first]
+    if mode:
+        y = eng.cazac_cancel(seqs[d], y, est[d], size_multiplier=m, dtype=dtype)
+    for u in others:
+        est[u] = estimate(u, y)
+    if mode == 2 and len(others) > 1:
+        norms = np.stack([np.linalg.norm(est[u].reshape(len(y), -1).astype(np.complex128), axis=1) for u in others], axis=1)
+        # descending; on a tie the higher index first: sort by (-norm, -index)
+        idx = np.asarray(others)
+        orders = np.stack([idx[np.lexsort((-idx, -row))] for row in norms]) if len(y) else np.zeros((0, len(others)), int)
+        for order in {tuple(o) for o in orders.tolist()}:
+            rows = np.flatnonzero((orders == np.asarray(order)).all(axis=1))
+            res = y[rows]
+            for s in range(1, len(order)):
+                res = eng.cazac_cancel(seqs[order[s - 1]], res, est[order[s - 1]][rows], size_multiplier=m, dtype=dtype)
+                est[order[s]][rows] = estimate(order[s], res)
+    out = np.stack(est, axis=2)                                   # [B, Nr, n_users, m Ne]
+    return out.reshape(tuple(lead) + out.shape[1:])

@@ -1151,6 +1151,70 @@ class Engine:
         res = {"n_realizations": int(count), "err": tot[0], "pow": tot[1]}
         return (res, e, p) if per_realization else res
 
+    # ---- interference cancellation (csrc/kernels_chanest_ic.hip) --------------------------------------
+    def cazac_cancel(self, ref_seq, rx, est, size_multiplier=2, dtype=None, out=None):
+        """rx - est[..., ::size_multiplier] * ref_seq: the contribution of an estimated user taken out of the comb.  ref_seq
+        [ne]; rx [..., ne]; est [..., size_multiplier * ne] as cazac_estimate returns it.  out: a DeviceArray shaped like rx
+        to write into (rx itself: in place), which is then also what is returned."""
+        dt = self._dt(dtype)
+        d_ref, _ = self._cin(ref_seq, dt)
+        d_rx, host = self._cin(rx, dt)
+        d_est, _ = self._cin(est, dt)
+        ne, m = d_ref.size, int(size_multiplier)
+        if d_rx.shape[-1] != ne or tuple(d_est.shape) != tuple(d_rx.shape[:-1]) + (m * ne,):
+            raise ValueError("rx must be [..., ne = %d] and est [..., %d] over the same rows (got %s, %s)"
+                             % (ne, m * ne, d_rx.shape, d_est.shape))
+        if out is None:
+            out = self.empty(d_rx.shape, _lib.np_complex(dt))
+        elif not isinstance(out, DeviceArray) or out.dtype != d_rx.dtype or tuple(out.shape) != tuple(d_rx.shape):
+            raise ValueError("out must be a device array with rx's shape and type")
+        else:
+            host = False
+        self._raise_value(self.lib.mcle_cazac_cancel(self.ctx, dt, d_ref.ptr, ne, d_rx.ptr, d_est.ptr, d_rx.size // max(ne, 1), m,
+                                                     out.ptr))
+        return self._out(out, host)
+
+    def run_chanest_ic(self, ref_seqs, n_rx, num_taps_to_keep, size_multiplier, noise_var, tap_power, tap_delay, seed, first,
+                       count, mode, direct_user=0, link_gain=None, normalized=False, dtype=None, per_realization=False,
+                       return_order=False):
+        """run_chanest with a linear power gain per user (link_gain, default all 1) and interference cancellation at the
+        receiver of `direct_user` (mcle_run_chanest_ic).  mode 0 / 'none': every user from the received comb; 1 / 'direct':
+        the direct user is estimated and subtracted first; 2 / 'sic': then the others in descending order of the norm of their
+        first estimates, each estimated from the residual left by all stronger ones.  Returns what run_chanest returns; with
+        return_order=True the int32 array [count, n_users] of the order of the final estimates is appended."""
+        dt = self._dt(dtype)
+        seqs = np.atleast_2d(np.asarray(ref_seqs))
+        n_users = int(seqs.shape[0])
+        d_seq = self.to_device(seqs, _lib.np_complex(dt))
+        ic = _lib.ChanestIcCfg()
+        cfg = ic.base
+        cfg.ne, cfg.size_multiplier, cfg.num_taps_to_keep = int(seqs.shape[1]), int(size_multiplier), int(num_taps_to_keep)
+        cfg.n_users, cfg.n_rx, cfg.n_taps, cfg.normalized = n_users, int(n_rx), len(tap_delay), 1 if normalized else 0
+        cfg.noise_var = float(noise_var)
+        if len(tap_delay) > _lib.MAX_TAPS or len(tap_power) != len(tap_delay):
+            raise ValueError("at most %d taps; powers and delays must match" % _lib.MAX_TAPS)
+        for i, (p, d) in enumerate(zip(tap_power, tap_delay)):
+            cfg.tap_power[i], cfg.tap_delay[i] = float(p), int(d)
+        cfg.d_ref_seq = d_seq.ptr
+        ic.mode, ic.direct_user = int(_lib.CHANEST_IC_MODES.get(mode, mode)), int(direct_user)
+        gains = np.ones(n_users) if link_gain is None else np.asarray(link_gain, dtype=np.float64).reshape(-1)
+        if gains.size != n_users:
+            raise ValueError("link_gain must hold one gain per user (%d users, got %d)" % (n_users, gains.size))
+        for u in range(min(n_users, 8)):
+            ic.link_gain[u] = float(gains[u])
+        err, pw = self.empty((count, n_users), np.float64), self.empty((count, n_users), np.float64)
+        order = self.empty((count, n_users), np.int32) if return_order else None
+        self._raise_value(self.lib.mcle_run_chanest_ic(self.ctx, dt, byref(ic), int(seed), int(first), int(count), err.ptr,
+                                                       pw.ptr, order.ptr if return_order else None))
+        e, p = err.get(), pw.get()
+        # (cumsum adds strictly in index order; a plain sum may go pairwise)
+        tot = [np.cumsum(v, axis=0)[-1] if count else np.zeros(n_users) for v in (e, p)]
+        res = {"n_realizations": int(count), "err": tot[0], "pow": tot[1]}
+        ret = (res, e, p) if per_realization else (res,)
+        if return_order:
+            ret = ret + (order.get(),)
+        return ret if len(ret) > 1 else res
+
     # ---- same-seed parity mode (NumPy legacy RandomState on the device) ----------------------
     def legacy_draws(self, program, seed_base, first, count):
         """program: list of ('randint', n, range) / ('randn', n) / ('rand', n).  Realization r gets

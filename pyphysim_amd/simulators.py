@@ -347,15 +347,22 @@ class IaSimulator(_LinkSimulator):
 
 class ChannelEstimationSimulator(BatchedSimulationRunner):
     """Estimation-error Monte Carlo of the CAZAC-based channel estimator (the experiment of the reference's
-    apps/simple_precoded_srs.py, without its interference-cancellation variants): `n_users` users send the SRS
-    sequences of one root (cyclic shifts `shifts`) on the same comb of `Ne` positions, every (user, receive antenna)
-    link is a block-static tapped delay line with the given profile (integer delays on the size_multiplier * Ne
-    subcarrier grid), and every user is estimated with `num_taps_to_keep`.  One call into libmcle per batch
-    (Engine.run_chanest).  Results: 'nmse_user{u}' = RATIO(sum |H^ - H|^2, sum |H|^2), 'elapsed_time'."""
+    apps/simple_precoded_srs.py): `n_users` users send the SRS sequences of one root (cyclic shifts `shifts`) on the
+    same comb of `Ne` positions, every (user, receive antenna) link is a block-static tapped delay line with the given
+    profile (integer delays on the size_multiplier * Ne subcarrier grid), and every user is estimated with
+    `num_taps_to_keep`.  One call into libmcle per batch (Engine.run_chanest).
+    Results: 'nmse_user{u}' = RATIO(sum |H^ - H|^2, sum |H|^2), 'elapsed_time'.
+
+    The app's interference-cancellation rules at the receiver of `direct_user`: interference_cancellation='direct' estimates
+    that user first and subtracts its contribution before the others are estimated, 'sic' then goes on through the others
+    in descending order of their first estimates' norm; `pathloss` is a linear power gain per user (the app's unequal path
+    losses are what makes the rules matter), `root_indexes` one root per user as the app has it (the shifts may then
+    coincide).  A rule other than 'none' or a pathloss routes the batches through Engine.run_chanest_ic; otherwise run_chanest."""
 
     def __init__(self, SNR, n_users=3, shifts=None, Ne=150, size_multiplier=2, num_taps_to_keep=15, Nr=4, root_index=25,
                  tap_powers_dB=(0.0, -3.0, -6.0, -9.0), tap_delays=(0, 1, 2, 4), rep_max=1000, seed=0, batch_size=4096,
-                 dtype="f32", engine=None, common_random_numbers=False, process_group=None):
+                 dtype="f32", engine=None, common_random_numbers=False, process_group=None,
+                 interference_cancellation="none", direct_user=0, pathloss=None, root_indexes=None):
         super().__init__(batch_size=batch_size, process_group=process_group)
         from .reference_signals import RootSequence, SrsUeSequence
         self.rep_max = rep_max
@@ -364,10 +371,26 @@ class ChannelEstimationSimulator(BatchedSimulationRunner):
         self.common_random_numbers = common_random_numbers
         self._engine = engine
         shifts = tuple(range(n_users)) if shifts is None else tuple(int(s) for s in shifts)
-        if len(shifts) != n_users or len(set(shifts)) != n_users:
-            raise ValueError("shifts must name one distinct cyclic shift per user")
-        root = RootSequence(root_index=int(root_index), size=int(Ne))
-        self.ref_seqs = np.stack([SrsUeSequence(root, s).seq_array() for s in shifts])
+        if root_indexes is None:
+            if len(shifts) != n_users or len(set(shifts)) != n_users:
+                raise ValueError("shifts must name one distinct cyclic shift per user")
+            root = RootSequence(root_index=int(root_index), size=int(Ne))
+            self.ref_seqs = np.stack([SrsUeSequence(root, s).seq_array() for s in shifts])
+        else:
+            roots = tuple(int(u) for u in root_indexes)
+            if len(roots) != n_users or len(shifts) != n_users or len(set(zip(roots, shifts))) != n_users:
+                raise ValueError("root_indexes and shifts must name one distinct (root, cyclic shift) pair per user")
+            self.ref_seqs = np.stack([SrsUeSequence(RootSequence(root_index=u, size=int(Ne)), s).seq_array()
+                                      for u, s in zip(roots, shifts)])
+        if interference_cancellation not in _lib.CHANEST_IC_MODES:
+            raise ValueError("interference_cancellation must be 'none', 'direct' or 'sic'")
+        if not 0 <= int(direct_user) < n_users:
+            raise ValueError("direct_user must be one of the %d users" % n_users)
+        self._link_gain = None if pathloss is None else np.asarray(pathloss, dtype=float).reshape(-1)
+        if self._link_gain is not None and self._link_gain.size != n_users:
+            raise ValueError("pathloss must hold one linear gain per user")
+        self._ic_mode, self._direct_user = interference_cancellation, int(direct_user)
+        self._plain = interference_cancellation == "none" and pathloss is None
         self._tap_power = 10.0 ** (np.asarray(tap_powers_dB, dtype=float) / 10.0)
         self._tap_power = self._tap_power / self._tap_power.sum()
         self._tap_delay = [int(d) for d in tap_delays]
@@ -383,9 +406,13 @@ class ChannelEstimationSimulator(BatchedSimulationRunner):
 
     def _run_batch(self, current_parameters, first_rep, count):
         p = current_parameters
-        res, err, pw = self.engine.run_chanest(self.ref_seqs, p["Nr"], p["num_taps_to_keep"], p["size_multiplier"],
-                                               1.0 / float(dB2Linear(p["SNR"])), self._tap_power, self._tap_delay,
-                                               self._seed_for(p), first_rep, count, dtype=self.dtype, per_realization=True)
+        args = (self.ref_seqs, p["Nr"], p["num_taps_to_keep"], p["size_multiplier"], 1.0 / float(dB2Linear(p["SNR"])),
+                self._tap_power, self._tap_delay, self._seed_for(p), first_rep, count)
+        if self._plain:
+            res, err, pw = self.engine.run_chanest(*args, dtype=self.dtype, per_realization=True)
+        else:
+            res, err, pw = self.engine.run_chanest_ic(*args, self._ic_mode, direct_user=self._direct_user,
+                                                      link_gain=self._link_gain, dtype=self.dtype, per_realization=True)
         c = {k: 0 for k in self.COUNTER_KEYS + ("n_symbols", "n_bits")}
         c["n_realizations"] = int(count)
         ratio = np.cumsum(err / pw, axis=0)[-1] if count else np.zeros(p["n_users"])

@@ -1,7 +1,8 @@
 // Stand-alone host program for the sanitizer build of the C ABI's channel-estimation entry points: every argument rule of
-// mcle_cazac_estimate and mcle_run_chanest is driven with a context built on the host (no device is opened: each call returns
+// mcle_cazac_estimate, mcle_run_chanest, mcle_cazac_cancel and mcle_run_chanest_ic is driven with a context built on the host (no device is opened: each call returns
 // from its checks, or fails at the first device call after them).  Built by `make -C pyphysim_amd/csrc asan-argcheck SAN=...`
 // ("Host sanitizer runs"), exits non-zero on the first unexpected return code.
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -71,6 +72,72 @@ int main() {
     c = good, c.d_ref_seq = nullptr;
     EXPECT(mcle_run_chanest(&ctx, MCLE_F64, &c, 1, 0, 4, d, d), false, "null array");
     EXPECT(mcle_run_chanest(&ctx, MCLE_F32, &good, 1, 0, 0, d, d), true, "");
+
+    EXPECT(mcle_cazac_cancel(nullptr, MCLE_F64, p, 48, p, p, 1, 2, p), false, "null context");
+    EXPECT(mcle_cazac_cancel(&ctx, 7, p, 48, p, p, 1, 2, p), false, "dtype");
+    EXPECT(mcle_cazac_cancel(&ctx, MCLE_F64, p, 1, p, p, 1, 2, p), false, "at least 2");
+    EXPECT(mcle_cazac_cancel(&ctx, MCLE_F64, p, 48, p, p, 1, 0, p), false, "size_multiplier");
+    EXPECT(mcle_cazac_cancel(&ctx, MCLE_F64, p, 2049, p, p, 1, 2, p), false, "4096");
+    EXPECT(mcle_cazac_cancel(&ctx, MCLE_F64, p, 48, p, nullptr, 1, 2, p), false, "null array");
+    EXPECT(mcle_cazac_cancel(&ctx, MCLE_F32, p, 48, p, p, 1, 2, nullptr), false, "null array");
+    EXPECT(mcle_cazac_cancel(&ctx, MCLE_F32, p, 48, nullptr, nullptr, 0, 2, nullptr), true, "");
+
+    mcle_chanest_ic_cfg ig;
+    std::memset(&ig, 0, sizeof(ig));
+    ig.base = good, ig.mode = 2, ig.direct_user = 1;
+    for (int u = 0; u < 3; ++u) ig.link_gain[u] = 0.5;          // users 3 .. 7 stay 0: not read
+    int32_t* o = reinterpret_cast<int32_t*>(buf.data());
+    EXPECT(mcle_run_chanest_ic(nullptr, MCLE_F64, &ig, 1, 0, 4, d, d, o), false, "null argument");
+    EXPECT(mcle_run_chanest_ic(&ctx, MCLE_F64, nullptr, 1, 0, 4, d, d, o), false, "null argument");
+    EXPECT(mcle_run_chanest_ic(&ctx, 5, &ig, 1, 0, 4, d, d, o), false, "dtype");
+    mcle_chanest_ic_cfg ic = ig;
+    ic.base.ne = 1;
+    EXPECT(mcle_run_chanest_ic(&ctx, MCLE_F64, &ic, 1, 0, 4, d, d, o), false, "at least 2");
+    ic = ig, ic.base.size_multiplier = 0;
+    EXPECT(mcle_run_chanest_ic(&ctx, MCLE_F64, &ic, 1, 0, 4, d, d, o), false, "size_multiplier");
+    ic = ig, ic.base.ne = 2049;
+    EXPECT(mcle_run_chanest_ic(&ctx, MCLE_F64, &ic, 1, 0, 4, d, d, o), false, "4096");
+    ic = ig, ic.base.num_taps_to_keep = 48;
+    EXPECT(mcle_run_chanest_ic(&ctx, MCLE_F64, &ic, 1, 0, 4, d, d, o), false, "num_taps_to_keep");
+    ic = ig, ic.base.n_users = 9;
+    EXPECT(mcle_run_chanest_ic(&ctx, MCLE_F64, &ic, 1, 0, 4, d, d, o), false, "n_users");
+    ic = ig, ic.base.n_rx = 0;
+    EXPECT(mcle_run_chanest_ic(&ctx, MCLE_F64, &ic, 1, 0, 4, d, d, o), false, "n_rx");
+    ic = ig, ic.base.n_taps = 0;
+    EXPECT(mcle_run_chanest_ic(&ctx, MCLE_F64, &ic, 1, 0, 4, d, d, o), false, "n_taps");
+    ic = ig, ic.base.tap_delay[1] = 48;
+    EXPECT(mcle_run_chanest_ic(&ctx, MCLE_F64, &ic, 1, 0, 4, d, d, o), false, "tap delays");
+    ic = ig, ic.base.tap_power[1] = -0.5;
+    EXPECT(mcle_run_chanest_ic(&ctx, MCLE_F64, &ic, 1, 0, 4, d, d, o), false, "tap powers");
+    ic = ig, ic.base.noise_var = -1.0;
+    EXPECT(mcle_run_chanest_ic(&ctx, MCLE_F64, &ic, 1, 0, 4, d, d, o), false, "noise variance");
+    ic = ig, ic.base.tap_power[0] = 0.0, ic.base.tap_power[1] = 0.0;
+    EXPECT(mcle_run_chanest_ic(&ctx, MCLE_F64, &ic, 1, 0, 4, d, d, o), false, "sum to zero");
+    EXPECT(mcle_run_chanest_ic(&ctx, MCLE_F64, &ig, 1, 0, 1ull << 31, d, d, o), false, "2^31");
+    ic = ig, ic.mode = 3;
+    EXPECT(mcle_run_chanest_ic(&ctx, MCLE_F64, &ic, 1, 0, 4, d, d, o), false, "mode");
+    ic = ig, ic.mode = -1;
+    EXPECT(mcle_run_chanest_ic(&ctx, MCLE_F64, &ic, 1, 0, 4, d, d, o), false, "mode");
+    ic = ig, ic.direct_user = 3;
+    EXPECT(mcle_run_chanest_ic(&ctx, MCLE_F64, &ic, 1, 0, 4, d, d, o), false, "direct_user");
+    ic = ig, ic.direct_user = -1;
+    EXPECT(mcle_run_chanest_ic(&ctx, MCLE_F64, &ic, 1, 0, 4, d, d, o), false, "direct_user");
+    ic = ig, ic.link_gain[2] = 0.0;                             // the last gain that is read
+    EXPECT(mcle_run_chanest_ic(&ctx, MCLE_F64, &ic, 1, 0, 4, d, d, o), false, "link gains");
+    ic = ig, ic.link_gain[0] = -1.0;
+    EXPECT(mcle_run_chanest_ic(&ctx, MCLE_F64, &ic, 1, 0, 4, d, d, o), false, "link gains");
+    ic = ig, ic.link_gain[1] = std::nan("");
+    EXPECT(mcle_run_chanest_ic(&ctx, MCLE_F64, &ic, 1, 0, 4, d, d, o), false, "link gains");
+    ic = ig, ic.link_gain[1] = HUGE_VAL;
+    EXPECT(mcle_run_chanest_ic(&ctx, MCLE_F64, &ic, 1, 0, 4, d, d, o), false, "link gains");
+    ic = ig, ic.base.d_ref_seq = nullptr;
+    EXPECT(mcle_run_chanest_ic(&ctx, MCLE_F64, &ic, 1, 0, 4, d, d, o), false, "null array");
+    EXPECT(mcle_run_chanest_ic(&ctx, MCLE_F64, &ig, 1, 0, 4, d, nullptr, o), false, "null array");
+    // one realization beyond the LDS of a compute unit: 8 users x 4 antennas x 2048 kept taps of complex128 (decided on the host)
+    ic = ig, ic.base.ne = 2048, ic.base.num_taps_to_keep = 2047, ic.base.n_users = 8, ic.base.n_rx = 4;
+    for (int u = 0; u < 8; ++u) ic.link_gain[u] = 1.0;
+    EXPECT(mcle_run_chanest_ic(&ctx, MCLE_F64, &ic, 1, 0, 4, d, d, o), false, "does not fit");
+    EXPECT(mcle_run_chanest_ic(&ctx, MCLE_F32, &ig, 1, 0, 0, d, d, nullptr), true, "");
     char name[64] = "x";
     mcle_ctx_last_kernel(&ctx, name, sizeof(name));
     if (name[0] != 0) {
