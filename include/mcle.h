@@ -192,7 +192,15 @@ enum {
                                       otherwise: no table gathers, and the decisions of the exhaustive sweep by a margin argument
                                       that holds for |re|, |im| up to ~2^11 level spacings in complex128 (beyond that -- an
                                       equaliser output in a fade of -66 dB -- the identity rests on test coverage: the chance that
-                                      such a point also sits within 2^-30 of a boundary is ~1e-14 per symbol)); likewise for a
+                                      such a point also sits within 2^-30 of a boundary is ~1e-14 per symbol).  complex128, four
+                                      decisions at a time (walk_f64.hpp: walk_qam_fixed4): the margin is first tested in FIXED
+                                      POINT -- q = (int) fma(e, hs 2^24, (hl + 1/2) 2^24) clamped to [2^23, lm1 2^24 + 2^23],
+                                      level q >> 24, accepted when the fraction q & (2^24 - 1) keeps 2 counts off either end,
+                                      i.e. 2^-23 of a spacing off every boundary; the multiply-add rounds by <= 2^-25 counts, so
+                                      an accepted axis has |t - level| < 1/2 - (2 - 2^-25) 2^-24 < 1/2 - 2^-30 for the f64 t as
+                                      well: the f64 certificate accepts it too, with the same level (NaN / out of range saturate
+                                      onto a clamped end, accepted on both sides); a group with an axis inside 2^-23 takes the f64
+                                      certificate above, unchanged, and behind it the table search); likewise for a
                                       four-point constellation with one point per quadrant at (+-a, +-b) -- QPSK -- decided by the
                                       signs (demod_quad_cert: certified for 2^-30 min(a, b) <= |re|, |im| <= 2^8 max(a, b)), and for
                                       8- / 16-PSK inside the table search itself (demod_psk_cert: the sector by sign masks and one

@@ -113,22 +113,15 @@ __device__ __forceinline__ int walk_qam_slicer(double2 r, double scale, int L, i
     return (int)(((v >> 8) << half_bits) | (v & 0xFFu));
 }
 
-// complex128, square QAM, FOUR decisions counted in the LEVEL domain (the complex64 pipelines' trick, qam_pack.hpp): the decided levels
-// (row << hb | column, a byte per symbol) are compared with the sent labels turned into levels (one shift-and-xor for all four), and
-// the bit errors follow from one field-wise prefix xor of the difference word -- no Gray decode and no label per decision: ~18
-// instead of ~27 instructions per decision.  CERT: demod_qam_cert's margin test (same t, same clamp, same rint, same bound); a symbol
-// it does not vouch for takes the literal sweep, whose label goes back to the level domain.  !CERT: the slicer's floor(t + 1/2).
-// `sent`: the four labels, a byte each.
+// complex128, square QAM, FOUR decisions in the LEVEL domain (the complex64 pipelines' trick, qam_pack.hpp): the decided levels
+// (row << hb | column, a byte per symbol) of four estimates.  CERT: demod_qam_cert's margin test (same t, same clamp, same rint, same
+// bound); a symbol it does not vouch for takes the literal sweep, whose label goes back to the level domain.  !CERT: the slicer's
+// floor(t + 1/2).  This is the f64-pipe form: since round 12 the complex128 certificate reaches it only from a group its fixed-point
+// test (walk_qam_fixed4 below) does not vouch for.
 template <typename T, bool CERT>
-__device__ __forceinline__ void walk_qam_count4(const ModemParams<T>& mp, const cx<T>* __restrict__ s_table, const cx<T> (&e)[4],
-                                                uint32_t sent, unsigned& se, unsigned& be) {
-    static_assert(sizeof(T) == 8 || CERT, "complex64 slices in the packed form (qam_levels4)");
+__device__ __forceinline__ uint32_t walk_qam_levels4(const ModemParams<T>& mp, const cx<T>* __restrict__ s_table, const cx<T> (&e)[4]) {
     const int hb = mp.half_bits;
     const uint32_t fm = (1u << hb) - 1u;
-    QamPack qp;
-    qp.hb = hb;
-    qp.m1 = (((fm >> 1) | ((fm >> 1) << hb)) & 0xFFu) * 0x01010101u;
-    qp.m2 = (((fm >> 2) | ((fm >> 2) << hb)) & 0xFFu) * 0x01010101u;
     const T lm1 = (T)(mp.qam_L - 1), hs = mp.qam_scale * (T)0.5, hl = lm1 * (T)0.5;
     constexpr T lim = sizeof(T) == 8 ? (T)(0.5 - 0x1p-30) : (T)(0.5 - 0x1p-15);      // demod_qam_cert's margins
     [[maybe_unused]] const T rmax = ((T)16 + hl) / hs;                      // complex64: the certificate's range (wave-uniform)
@@ -156,14 +149,93 @@ __device__ __forceinline__ void walk_qam_count4(const ModemParams<T>& mp, const 
     }
     if constexpr (CERT) {
         if (!all) {
+            const uint32_t g1 = ((fm >> 1) | ((fm >> 1) << hb)) & 0xFFu;     // (QamPack::m1 of one byte)
 #pragma unroll
             for (int i = 0; i < 4; ++i)
                 if (!sure[i]) {
                     const uint32_t lab = (uint32_t)walk_sweep<T>(s_table, mp.M, e[i]);
-                    const uint32_t lev = lab ^ ((lab >> 1) & (qp.m1 & 0xFFu));
+                    const uint32_t lev = lab ^ ((lab >> 1) & g1);
                     lv = (lv & ~(0xFFu << (8 * i))) | (lev << (8 * i));
                 }
         }
+    }
+    return lv;
+}
+
+// Round 12: THE COMPLEX128 CERTIFICATE IN FIXED POINT.  Everything behind the first multiply-add of demod_qam_cert only asks which
+// integer t = e hs + hl is nearest to and whether t keeps 2^-30 off a half-integer; here that question is put to the 32-bit integer
+// pipe.  Per axis (the imaginary one with -hs), S = 24, delta = 2, c1 = hs 2^S, c0 = (hl + 1/2) 2^S (both scalings exact):
+//   q = (int) fma(e, c1, c0)                      = floor((t + 1/2) 2^S) wherever the clamp below does not take over
+//   q = med3(q, 2^(S-1), lm1 2^S + 2^(S-1))       the certificate's clamp of t to [0, lm1]
+//   level k = q >> S, fraction f = q & (2^S - 1);  the axis is VOUCHED iff delta <= f <= 2^S - 1 - delta.
+// The eight axes of a group share ONE unsigned test: the maximum of (q - delta) << 8 -- the 24 bits of (q - delta) & (2^S - 1) moved
+// to the top of the word, which keeps their order; the shift and the subtraction are one v_lshl_add_u32 -- against
+// (2^S - 1 - 2 delta) << 8.  The levels are the top bytes of the q words: three byte permutes gather four of them.
+// A group that is not vouched takes walk_qam_levels4 above on the unaltered e: the f64 margin test, then the sweep.
+// Why no count can move (by construction, not by probability).  Let te = e hs + hl exactly.  The one rounding of the multiply-add is
+// at most 2^-25 counts (|q| < 2^28: byte-packed levels mean lm1 <= 15), so te + 1/2 lies in [q - 2^-25, q + 1 + 2^-25) 2^-S.  A vouched
+// axis therefore has |te - k| < 1/2 - (delta - 2^-25) 2^-S.  The f64 certificate's t = fl(te) is within 2^-50 of te, hence
+// |t - k| < 1/2 - 2^-30: it vouches too, and rint(t) = k -- every vouched axis is an axis demod_qam_cert vouches for, with the same
+// level.  Monotone clamps commute with both.  NaN and out-of-range inputs saturate in v_cvt_i32_f64 (NaN -> 0) and land on a clamped
+// end with f = 2^(S-1): vouched, level 0 or lm1, as fmin / fmax leave them in demod_qam_cert.  (The conversion and the median are
+// written as instructions: an out-of-range cast has no defined value in C++, and the compiler forms v_med3_i32 for constant
+// bounds only.)  Unvouched axes become 2^7 times more frequent, ~2e-7 per axis: still nothing per wavefront.
+constexpr int kWalkFixShift = 24;            // S
+constexpr uint32_t kWalkFixDelta = 2u;       // delta
+// q of one axis: conversion and clamp, one after the other (v_cvt_i32_f64 is an ordinary VALU instruction: its result may be read
+// by the next one, as the compiler's own code does; one operand of a VOP3 may be scalar: hi)
+__device__ __forceinline__ int walk_fix_q(double x, int lo, int hi) {
+    int q = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("v_cvt_i32_f64 %0, %1\n\tv_med3_i32 %0, %0, %2, %3" : "=&v"(q) : "v"(x), "v"(lo), "s"(hi));
+#endif
+    return q;
+}
+// the level word of four estimates; false: some axis of the group is not vouched (the word then means nothing)
+__device__ __forceinline__ bool walk_qam_fixed4(const ModemParams<double>& mp, const double2 (&e)[4], uint32_t& lv) {
+    constexpr int S = kWalkFixShift;
+    constexpr uint32_t kOff = (0u - kWalkFixDelta) << 8, kBound = ((1u << S) - 1u - 2u * kWalkFixDelta) << 8;
+    const double hs = mp.qam_scale * 0.5, hl = (double)(mp.qam_L - 1) * 0.5;
+    const double c1 = hs * (double)(1 << S), c0 = (hl + 0.5) * (double)(1 << S);
+    const int lo = 1 << (S - 1), hi = ((mp.qam_L - 1) << S) + (1 << (S - 1));
+    int qj[4], qi[4];
+    uint32_t worst = 0u;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        qj[i] = walk_fix_q(__builtin_fma(e[i].x, c1, c0), lo, hi);
+        qi[i] = walk_fix_q(__builtin_fma(e[i].y, -c1, c0), lo, hi);
+        const uint32_t fj = ((uint32_t)qj[i] << 8) + kOff, fi = ((uint32_t)qi[i] << 8) + kOff;
+        worst = max(max(worst, fj), fi);
+    }
+    // v_perm_b32: selector byte 0 - 3 = that byte of the SECOND source, 4 - 7 = of the first, 0x0c = zero
+    const uint32_t j01 = __builtin_amdgcn_perm((uint32_t)qj[1], (uint32_t)qj[0], 0x0c0c0703u);
+    const uint32_t j23 = __builtin_amdgcn_perm((uint32_t)qj[3], (uint32_t)qj[2], 0x0c0c0703u);
+    const uint32_t i01 = __builtin_amdgcn_perm((uint32_t)qi[1], (uint32_t)qi[0], 0x0c0c0703u);
+    const uint32_t i23 = __builtin_amdgcn_perm((uint32_t)qi[3], (uint32_t)qi[2], 0x0c0c0703u);
+    const uint32_t wj = __builtin_amdgcn_perm(j23, j01, 0x05040100u), wi = __builtin_amdgcn_perm(i23, i01, 0x05040100u);
+    lv = (wi << mp.half_bits) | wj;
+    return worst <= kBound;
+}
+
+// FOUR decisions counted in the level domain: the decided levels are compared with the sent labels turned into levels (one
+// shift-and-xor for all four), and the bit errors follow from one field-wise prefix xor of the difference word -- no Gray decode and no
+// label per decision.  `sent`: the four labels, a byte each.  complex128 with the certificate: the fixed-point form, the f64 form
+// for the groups it declines; everything else: the f64 form.
+template <typename T, bool CERT>
+__device__ __forceinline__ void walk_qam_count4(const ModemParams<T>& mp, const cx<T>* __restrict__ s_table, const cx<T> (&e)[4],
+                                                uint32_t sent, unsigned& se, unsigned& be) {
+    static_assert(sizeof(T) == 8 || CERT, "complex64 slices in the packed form (qam_levels4)");
+    const int hb = mp.half_bits;
+    const uint32_t fm = (1u << hb) - 1u;
+    QamPack qp;
+    qp.hb = hb;
+    qp.m1 = (((fm >> 1) | ((fm >> 1) << hb)) & 0xFFu) * 0x01010101u;
+    qp.m2 = (((fm >> 2) | ((fm >> 2) << hb)) & 0xFFu) * 0x01010101u;
+    uint32_t lv;
+    if constexpr (CERT && sizeof(T) == 8) {
+        if (__builtin_expect(!walk_qam_fixed4(mp, e, lv), 0)) lv = walk_qam_levels4<T, CERT>(mp, s_table, e);
+    } else {
+        lv = walk_qam_levels4<T, CERT>(mp, s_table, e);
     }
     qam_count4(lv ^ labels_to_levels(sent, qp), qp, se, be);
 }
