@@ -804,6 +804,53 @@ typedef struct mcle_chanest_ic_cfg {
 int mcle_run_chanest_ic(mcle_ctx* ctx, int dtype, const mcle_chanest_ic_cfg* cfg, uint64_t seed, uint64_t first,
                         uint64_t count, double* d_err, double* d_pow, int32_t* d_order);
 
+/* ---- LS and MMSE block-pilot channel estimators (channel_estimation/estimators.py:12-61 compute_ls_estimation, :100-174
+ *      compute_mmse_estimation; Fodor et al. 2014) ---------------------------------------------------------------
+ * Model Y = h s + N: d_Y [batch][nr][n_pilots] row-major, d_out [batch][nr][nt], both complex of `dtype`; d_s [nt][n_pilots]
+ * when the pilots are shared (s_per_realization = 0, the reference's 2-D s), [batch][nt][n_pilots] when every realization
+ * has its own (s_per_realization = 1, the 3-D s).  The matched filter z = Y s^H is formed on chip, per realization.
+ * 1 <= nr <= 128, 1 <= n_pilots <= 1024.  batch = 0 returns MCLE_OK and launches nothing.  Outputs are bit-identical for
+ * any split of the batch.
+ *
+ * mcle_ls_estimate: out[b] = Y[b] s^H (s s^H)^-1; 1 <= nt <= 8, nt <= n_pilots.  The nt x nt Gram matrix is accumulated and
+ * inverted in f64 on chip, per realization, or once per workgroup when the pilots are shared.  A SINGULAR Gram matrix gives
+ * unspecified values (inf / nan), never a fault; the reference raises LinAlgError there.
+ * mcle_ctx_last_kernel: "ls_estimate f64|f32 nt<nt rounded up to a power of two>".
+ *
+ * mcle_mmse_estimate: nt = 1 (the reference asserts it; d_s is [n_pilots] or [batch][n_pilots]);
+ * out[b] = A (Y[b] s^H) n_pilots / |s|^2 with A = (noise_power I + n_pilots C)^-1 C, the reference's literal expression.
+ * cov: HOST pointer to C, [nr][nr] complex128 (interleaved re, im); null, noise_power < 0 or a value that is not finite is
+ * refused, and so is a singular noise_power I + n_pilots C.  A is computed at most once per call on the host in f64 (the
+ * last result is kept and reused while cov, n_pilots and noise_power stay the same) and applied on
+ * the matrix cores (v_mfma_f64_16x16x4_f64 / v_mfma_f32_16x16x4_f32) over tiles of 16 realizations per wavefront; it is read
+ * from global memory (L2) by every workgroup.  mcle_ctx_last_kernel: "mmse_estimate f64|f32 ga" (ga: A read from global
+ * memory, the only form).  Both functions return -1 for a violated rule, with a message that names the argument. */
+int mcle_ls_estimate(mcle_ctx* ctx, int dtype, const void* d_Y, const void* d_s, int nr, int nt, int n_pilots,
+                     int s_per_realization, size_t batch, void* d_out);
+int mcle_mmse_estimate(mcle_ctx* ctx, int dtype, const void* d_Y, const void* d_s, int nr, int n_pilots, int s_per_realization,
+                       size_t batch, double noise_power, const double* cov, void* d_out);
+
+/* Fused estimation-error Monte Carlo of the two estimators (the loop of the reference's
+ * tests/channel_estimation_package_test.py:246-325).  One realization: pilots s [nt][n_pilots] (drawn, or d_pilots);
+ * w [nr][nt] of CN(0, 1) and h = alpha L w; Y = h s + sqrt(noise_power) N with all nr n_pilots noise samples drawn; h^_LS as
+ * mcle_ls_estimate; with `cov` (needs nt = 1) h^_MMSE as mcle_mmse_estimate from the same Y.  Y is never stored.
+ * d_err_ls, d_err_mmse, d_pow [count]: |h^_LS - h|_F^2, |h^_MMSE - h|_F^2, |h|_F^2 per realization, every entry written;
+ * d_err_mmse may be NULL when cov is NULL.  They do not depend on the grid, on MCLE_OPT_GRID_OVERSUB or on how
+ * [first, first + count) is split; the caller sums in index order.  count = 0 returns MCLE_OK and launches nothing.
+ * Draws: DESIGN section 4 (pilot phases: stream 3, w: stream 2, noise: stream 1).  A shape whose working set does not
+ * fit the 160 KiB of LDS is refused ("does not fit").
+ * mcle_ctx_last_kernel: "pilot_mse f64|f32 b<realizations per wavefront> ls|ls+mmse" (+ " gl": L applied from global memory). */
+typedef struct mcle_pilot_mse_cfg {
+    int32_t nr, nt, n_pilots;           /* 1..128, 1..8, nt..256 */
+    int32_t random_pilots;              /* 1: drawn per realization, s = sqrt(pilot_power) e^{2 pi j u}; 0: d_pilots */
+    double pilot_power, noise_power, alpha;
+    const void* d_pilots;               /* DEVICE [nt][n_pilots], complex of the call's dtype; used when random_pilots = 0 */
+    const double* chan_factor;          /* HOST [nr][nr] complex128 L: h = alpha L w; NULL: L = I */
+    const double* cov;                  /* HOST [nr][nr] complex128: the C handed to the MMSE estimator; NULL: LS only */
+} mcle_pilot_mse_cfg;
+int mcle_run_pilot_mse(mcle_ctx* ctx, int dtype, const mcle_pilot_mse_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
+                       double* d_err_ls, double* d_err_mmse, double* d_pow);
+
 /* ---- same-seed parity mode: NumPy's legacy global RandomState replayed on the device -------
  * Realization r receives exactly what the reference draws after np.random.seed(seed_base + r)
  * (legacy MT19937; util/misc.py:327-355 randn_c = randn real block then imag block, and

@@ -136,6 +136,12 @@ class ChanestIcCfg(Structure):
 CHANEST_IC_MODES = {"none": 0, "direct": 1, "sic": 2}
 
 
+class PilotMseCfg(Structure):
+    _fields_ = [("nr", c_int32), ("nt", c_int32), ("n_pilots", c_int32), ("random_pilots", c_int32),
+                ("pilot_power", c_double), ("noise_power", c_double), ("alpha", c_double),
+                ("d_pilots", c_void_p), ("chan_factor", POINTER(c_double)), ("cov", POINTER(c_double))]
+
+
 class LegacySeg(Structure):
     _fields_ = [("kind", c_int32), ("n", c_int32), ("range", c_uint32), ("reserved", c_uint32)]
 
@@ -240,6 +246,9 @@ _PROTOS = {
     "mcle_run_chanest": (c_int, [_P, c_int, POINTER(ChanestCfg), c_uint64, c_uint64, c_uint64, _P, _P]),
     "mcle_cazac_cancel": (c_int, [_P, c_int, _P, c_int, _P, _P, c_size_t, c_int, _P]),
     "mcle_run_chanest_ic": (c_int, [_P, c_int, POINTER(ChanestIcCfg), c_uint64, c_uint64, c_uint64, _P, _P, _P]),
+    "mcle_ls_estimate": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_size_t, _P]),
+    "mcle_mmse_estimate": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, c_size_t, c_double, POINTER(c_double), _P]),
+    "mcle_run_pilot_mse": (c_int, [_P, c_int, POINTER(PilotMseCfg), c_uint64, c_uint64, c_uint64, _P, _P, _P]),
     "mcle_legacy_draws": (c_int, [_P, POINTER(LegacySeg), c_int, c_uint32, c_uint64, c_uint64, _P, c_size_t, _P,
                                   c_size_t, _P]),
     "mcle_complex_from_parts": (c_int, [_P, c_int, _P, _P, c_double, _P, c_size_t]),

@@ -1215,6 +1215,84 @@ class Engine:
             ret = ret + (order.get(),)
         return ret if len(ret) > 1 else res
 
+    # ---- LS / MMSE block-pilot estimators (csrc/kernels_estimators.hip) --------------------------------
+    @staticmethod
+    def _host_c128(M, nr, name):
+        """[nr, nr] complex matrix -> (contiguous complex128 array, POINTER(c_double) to its interleaved re, im)"""
+        M = np.ascontiguousarray(M, dtype=np.complex128)
+        if M.shape != (nr, nr):
+            raise ValueError("%s must be [%d, %d] (got %s)" % (name, nr, nr, M.shape))
+        return M, M.view(np.float64).ctypes.data_as(ctypes.POINTER(c_double))
+
+    def _pilot_args(self, Y, s, dt, nt_fixed=None):
+        """Y [batch, nr, P] and s [nt, P] or [batch, nt, P] -> device arrays, shapes and whether s is per realization"""
+        d_Y, host = self._cin(Y, dt)
+        d_s, _ = self._cin(s, dt)
+        if len(d_Y.shape) != 3 or len(d_s.shape) not in (2, 3):
+            raise ValueError("Y must be [batch, nr, n_pilots] and s [nt, n_pilots] or [batch, nt, n_pilots] (got %s, %s)"
+                             % (d_Y.shape, d_s.shape))
+        batch, nr, P = (int(v) for v in d_Y.shape)
+        per = len(d_s.shape) == 3
+        nt = int(d_s.shape[-2])
+        if int(d_s.shape[-1]) != P or (per and int(d_s.shape[0]) != batch):
+            raise ValueError("s %s does not match Y %s" % (d_s.shape, d_Y.shape))
+        if nt_fixed is not None and nt != nt_fixed:
+            raise ValueError("the MMSE estimator needs nt = %d (got %d)" % (nt_fixed, nt))
+        return d_Y, d_s, host, batch, nr, nt, P, per
+
+    def ls_estimate(self, Y, s, dtype=None):
+        """compute_ls_estimation on a batch: Y [batch, nr, P]; s [nt, P] (shared) or [batch, nt, P] -> Y s^H (s s^H)^-1,
+        [batch, nr, nt].  One launch (mcle_ls_estimate)."""
+        dt = self._dt(dtype)
+        d_Y, d_s, host, batch, nr, nt, P, per = self._pilot_args(Y, s, dt)
+        out = self.empty((batch, nr, nt), _lib.np_complex(dt))
+        self._raise_value(self.lib.mcle_ls_estimate(self.ctx, dt, d_Y.ptr, d_s.ptr, nr, nt, P, 1 if per else 0, batch, out.ptr))
+        return self._out(out, host)
+
+    def mmse_estimate(self, Y, s, noise_power, C, dtype=None):
+        """compute_mmse_estimation on a batch: Y [batch, nr, P]; s [1, P] or [batch, 1, P]; C [nr, nr] (host) ->
+        (noise_power I + P C)^-1 C (Y s^H) P / |s|^2, [batch, nr, 1].  One launch (mcle_mmse_estimate)."""
+        dt = self._dt(dtype)
+        d_Y, d_s, host, batch, nr, nt, P, per = self._pilot_args(Y, s, dt, nt_fixed=1)
+        C, c_ptr = self._host_c128(C, nr, "C")
+        out = self.empty((batch, nr, 1), _lib.np_complex(dt))
+        self._raise_value(self.lib.mcle_mmse_estimate(self.ctx, dt, d_Y.ptr, d_s.ptr, nr, P, 1 if per else 0, batch,
+                                                      float(noise_power), c_ptr, out.ptr))
+        return self._out(out, host)
+
+    def run_pilot_mse(self, nr, nt, n_pilots, noise_power, seed, first, count, pilot_power=1.0, alpha=1.0, pilots=None,
+                      chan_factor=None, cov=None, dtype=None, per_realization=False):
+        """Fused estimation-error Monte Carlo of the LS and MMSE estimators (mcle_run_pilot_mse): per realization pilots
+        (drawn with power pilot_power, or `pilots` [nt, n_pilots]), h = alpha chan_factor w, Y = h s + noise, both
+        estimates from the same Y; the MMSE one only with `cov` (the C handed to it; needs nt = 1).  Returns
+        dict(n_realizations, err_ls, err_mmse, pow): the sums over the realizations, in index order on the host, of
+        |h^ - h|_F^2 and |h|_F^2 (err_mmse None without cov); with per_realization=True also the three [count] arrays."""
+        dt = self._dt(dtype)
+        cfg = _lib.PilotMseCfg()
+        cfg.nr, cfg.nt, cfg.n_pilots = int(nr), int(nt), int(n_pilots)
+        cfg.pilot_power, cfg.noise_power, cfg.alpha = float(pilot_power), float(noise_power), float(alpha)
+        cfg.random_pilots = 1 if pilots is None else 0
+        keep = []
+        if pilots is not None:
+            d_p = self.to_device(np.asarray(pilots).reshape(int(nt), int(n_pilots)), _lib.np_complex(dt))
+            keep.append(d_p)
+            cfg.d_pilots = d_p.ptr
+        if chan_factor is not None:
+            L, cfg.chan_factor = self._host_c128(chan_factor, int(nr), "chan_factor")
+            keep.append(L)
+        if cov is not None:
+            Cm, cfg.cov = self._host_c128(cov, int(nr), "cov")
+            keep.append(Cm)
+        e_ls, pw = self.empty(count, np.float64), self.empty(count, np.float64)
+        e_mm = self.empty(count, np.float64) if cov is not None else None
+        self._raise_value(self.lib.mcle_run_pilot_mse(self.ctx, dt, byref(cfg), int(seed), int(first), int(count), e_ls.ptr,
+                                                      e_mm.ptr if e_mm is not None else None, pw.ptr))
+        arrs = [a.get() if a is not None else None for a in (e_ls, e_mm, pw)]
+        # (cumsum adds strictly in index order; a plain sum may go pairwise)
+        tot = [None if a is None else (float(np.cumsum(a)[-1]) if count else 0.0) for a in arrs]
+        res = {"n_realizations": int(count), "err_ls": tot[0], "err_mmse": tot[1], "pow": tot[2]}
+        return (res, arrs[0], arrs[1], arrs[2]) if per_realization else res
+
     # ---- same-seed parity mode (NumPy legacy RandomState on the device) ----------------------
     def legacy_draws(self, program, seed_base, first, count):
         """program: list of ('randint', n, range) / ('randn', n) / ('rand', n).  Realization r gets

@@ -431,3 +431,94 @@ class ChannelEstimationSimulator(BatchedSimulationRunner):
                                              float(c.get("pow_user%d" % u, 0.0)), float(c.get("nmse_user%d" % u, 0.0)),
                                              float(c.get("nmse_sq_user%d" % u, 0.0)), n))
         return res
+
+
+def _exact_limbs(values):
+    """Three integer-valued float64 sums whose weighted total (2^-8, 2^-34, 2^-60) is sum(values) to 2^-60 per value.  Each is
+    a sum of integers below 2^26 (for values below 2^18), exact in float64 up to 2^27 values -- so the totals a simulator
+    adds up over batches and ranks do not depend on how the realizations were grouped, which a float sum would."""
+    x = np.asarray(values, dtype=np.float64)
+    t1 = np.floor(x * 2.0 ** 8)
+    r1 = x - t1 * 2.0 ** -8
+    t2 = np.floor(r1 * 2.0 ** 34)
+    r2 = r1 - t2 * 2.0 ** -34
+    t3 = np.floor(r2 * 2.0 ** 60)
+    return tuple(float(t.sum()) for t in (t1, t2, t3))       # (integers: any order gives the same sum)
+
+
+def _from_limbs(c, key):
+    return (float(c.get(key + "_l0", 0.0)) * 2.0 ** -8 + float(c.get(key + "_l1", 0.0)) * 2.0 ** -34) \
+        + float(c.get(key + "_l2", 0.0)) * 2.0 ** -60
+
+
+class PilotEstimationSimulator(BatchedSimulationRunner):
+    """Estimation-error Monte Carlo of the LS and MMSE block-pilot estimators (the experiment of the reference's
+    tests/channel_estimation_package_test.py:246-325; Fodor et al. 2014): per realization `Nt` x `num_pilots` pilots of power
+    `pilot_power` (random phases when random_pilots, else the first rows of a DFT matrix), a channel h = alpha L w with w
+    `Nr` x `Nt` of CN(0, 1), Y = h s + noise of power 1 / SNR, and both estimates from the same Y.  With a covariance `C`
+    (`Nr` x `Nr`, Nt = 1) L = cholesky(C) and the MMSE estimator is handed alpha^2 C; without one L = I and only the LS
+    estimator runs.  One call into libmcle per batch (Engine.run_pilot_mse).
+
+    Results: 'mse_ls' = RATIO(sum |h^_LS - h|^2, alpha^2 n), the reference test's normalisation; 'mse_mmse' =
+    RATIO(sum |h^_MMSE - h|^2, n), only with C; 'channel_power' = RATIO(sum |h|^2, n); 'elapsed_time'.  The sums are kept as
+    exact integer limbs, so the results do not depend on batch_size or on the number of ranks."""
+
+    _SUMS = ("err_ls", "err_mmse", "pow")
+    # (the sums of squares only feed the confidence intervals and stay plain float sums)
+    EXTRA_KEYS = tuple("%s_l%d" % (k, i) for k in _SUMS for i in range(3)) + tuple(k + "_sq" for k in _SUMS)
+
+    def __init__(self, SNR, Nr=64, Nt=1, num_pilots=10, pilot_power=1.0, alpha=1.0, C=None, random_pilots=True,
+                 rep_max=5000, seed=0, batch_size=4096, dtype="f64", engine=None, common_random_numbers=False,
+                 process_group=None):
+        super().__init__(batch_size=batch_size, process_group=process_group)
+        self.rep_max = rep_max
+        self.seed = int(seed)
+        self.dtype = dtype
+        self.common_random_numbers = common_random_numbers
+        self._engine = engine
+        self._L = self._cov = None
+        if C is not None:
+            C = np.asarray(C, dtype=np.complex128)
+            if C.shape != (int(Nr), int(Nr)) or int(Nt) != 1:
+                raise ValueError("C must be [Nr, Nr] = [%d, %d] and needs Nt = 1 (the MMSE estimator is SIMO)" % (Nr, Nr))
+            self._L, self._cov = np.linalg.cholesky(C), float(alpha) ** 2 * C
+        self._pilots = None
+        if not random_pilots:
+            t, p = np.arange(int(Nt))[:, None], np.arange(int(num_pilots))[None, :]
+            self._pilots = np.sqrt(float(pilot_power)) * np.exp(-2j * np.pi * t * p / int(num_pilots))
+        self.params.add("SNR", np.atleast_1d(np.asarray(SNR, dtype=float)))
+        self.params.set_unpack_parameter("SNR")
+        for k, v in (("Nr", int(Nr)), ("Nt", int(Nt)), ("num_pilots", int(num_pilots)), ("pilot_power", float(pilot_power)),
+                     ("alpha", float(alpha)), ("random_pilots", bool(random_pilots))):
+            self.params.add(k, v)
+
+    engine = _LinkSimulator.engine
+    _seed_for = _LinkSimulator._seed_for
+
+    def _run_batch(self, current_parameters, first_rep, count):
+        p = current_parameters
+        res, e_ls, e_mm, pw = self.engine.run_pilot_mse(
+            p["Nr"], p["Nt"], p["num_pilots"], 1.0 / float(dB2Linear(p["SNR"])), self._seed_for(p), first_rep, count,
+            pilot_power=p["pilot_power"], alpha=p["alpha"], pilots=self._pilots, chan_factor=self._L, cov=self._cov,
+            dtype=self.dtype, per_realization=True)
+        c = {k: 0 for k in self.COUNTER_KEYS + ("n_symbols", "n_bits")}
+        c["n_realizations"] = int(count)
+        for key, arr in zip(self._SUMS, (e_ls, e_mm, pw)):
+            limbs = _exact_limbs(arr) if arr is not None else (0.0, 0.0, 0.0)
+            for i, v in enumerate(limbs):
+                c["%s_l%d" % (key, i)] = v
+            c[key + "_sq"] = float(np.square(arr).sum()) if arr is not None else 0.0
+        return c
+
+    def _results_from_counters(self, current_parameters, c):
+        from .simulations import Result, SimulationResults
+        n = max(int(c["n_realizations"]), 1)
+        a2 = current_parameters["alpha"] ** 2
+        res = SimulationResults()
+        e_ls, pw = _from_limbs(c, "err_ls"), _from_limbs(c, "pow")
+        res.add_result(Result.from_batch("mse_ls", Result.RATIOTYPE, e_ls, a2 * n, e_ls / a2, float(c.get("err_ls_sq", 0.0)) / a2 ** 2, n))
+        if self._cov is not None:
+            e_mm = _from_limbs(c, "err_mmse")
+            res.add_result(Result.from_batch("mse_mmse", Result.RATIOTYPE, e_mm, float(n), e_mm, float(c.get("err_mmse_sq", 0.0)), n))
+        res.add_result(Result.from_batch("channel_power", Result.RATIOTYPE, pw, float(n), pw, float(c.get("pow_sq", 0.0)), n))
+        return res
