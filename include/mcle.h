@@ -236,7 +236,9 @@ enum {
                                       kernel-vs-kernel tests: identical counters) */
     MCLE_OPT_STAGED_GENERIC = 16,  /* 1: every staged operator with more than one form (mcle_ctx_last_kernel lists them) takes its
                                       generic form whatever the pointers and the shape (A/B and form-vs-form tests) */
-    MCLE_OPT_COUNT = 17
+    MCLE_OPT_CODEBOOK_NO_PACK = 17, /* 1: the codebook kernels (mcle_chordal_min_dist, mcle_codebook_generate, mcle_run_codebook_search) take one
+                                      candidate per wavefront trip whatever its size (form-vs-form tests: identical outputs) */
+    MCLE_OPT_COUNT = 18
 };
 int mcle_ctx_set_option(mcle_ctx* ctx, int option, long long value);
 int mcle_ctx_get_option(mcle_ctx* ctx, int option, long long* value);
@@ -850,6 +852,54 @@ typedef struct mcle_pilot_mse_cfg {
 } mcle_pilot_mse_cfg;
 int mcle_run_pilot_mse(mcle_ctx* ctx, int dtype, const mcle_pilot_mse_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
                        double* d_err_ls, double* d_err_mmse, double* d_pow);
+
+/* ---- Grassmannian codebooks: chordal distances and the random search (subspace/metrics.py:21-113 calc_principal_angles,
+ *      calc_chordal_distance_from_principal_angles; apps/find_codebook.py:73-231 CodebookFinder) ---------------------------
+ * A codebook is K precoders [Nt][Ns], row-major, complex of the call's dtype.  Q_k: an orthonormal basis of the column space of
+ * precoder k (modified Gram-Schmidt with one re-orthogonalisation pass, on chip; the reference takes Householder QR -- the same
+ * subspace).  d^2(a, b) = Ns - sum_{s, s'} |q_{a,s}^H q_{b,s'}|^2, clamped at 0 (= sum_i sin^2 theta_i of the principal angles,
+ * the square of the reference's chordal distance).  The min distance of a codebook is the smallest d over the pairs a < b and
+ * its pair the first such pair in itertools.combinations order; the best candidate of a search is the one with the largest min
+ * d^2, ties to the lowest candidate index (the reference's strict >).
+ * Envelope: 2 <= Nt <= 8, 1 <= Ns <= min(Nt - 1, 4), 2 <= K, K * Ns <= 256; anything else is MCLE_E_INVAL with a message that
+ * names the argument (the shape rules are checked before the context).  The complex Gram matrix of the K Ns basis vectors is
+ * formed on the matrix cores (v_mfma_f64_16x16x4_f64 / v_mfma_f32_16x16x4_f32) as real products over the stacked [Re Q; Im Q].
+ * Outputs do not depend on the grid, on MCLE_OPT_GRID_OVERSUB, on the form (MCLE_OPT_CODEBOOK_NO_PACK) or on how the candidate
+ * range is split, bit for bit.
+ *
+ * mcle_chordal_min_dist: d_codebooks [n_codebooks][K][Nt][Ns] -> d_min_d2 [n_codebooks] (double), d_pair [n_codebooks][2]
+ * (int32); d_d2 (may be NULL) [n_codebooks][K][K]: the symmetric matrix of d^2 with a zero diagonal.  n_codebooks = 0 returns
+ * MCLE_OK and launches nothing.  mcle_ctx_last_kernel: "chordal_min_dist f64|f32 p<codebooks per wavefront trip>".
+ *
+ * mcle_codebook_generate: the candidates [first, first + count) of `seed` as they are BEFORE orthonormalisation, d_out
+ * [count][K][Nt][Ns].  Draws (mcle-philox-v1; realization = candidate index, flat entry index
+ * i = (k Nt + t) Ns + s): type 0 (complex) CN sample i of stream 2; type 1 (real) sqrt(2) x the real (even i) / imaginary (odd
+ * i) part of CN sample i / 2 of stream 2, imaginary part 0; both then divided by the precoder's Frobenius norm; type 2 (qegt)
+ * e^{j pi u_i}, u_i = uniform i of stream 3, not normalised (as the reference).
+ * mcle_ctx_last_kernel: "codebook_generate f64|f32 complex|real|qegt p<P>".
+ *
+ * mcle_run_codebook_search: generate, orthonormalise, Gram matrix, block sums, pair minimum and best candidate in one kernel; no
+ * codebook is stored.  Each wavefront keeps its running best over its trips and writes one record; a one-wavefront kernel picks
+ * among the records.  out (HOST): best_index is the candidate's index in [first, first + count).  d_min_d2 [count] and d_pair
+ * [count][2] (either may be NULL): every candidate's min d^2 and pair, every entry written.  count = 0 returns MCLE_OK with
+ * n_candidates = 0 and launches nothing.  Blocks until the result is on the host.
+ * mcle_ctx_last_kernel: "codebook_search f64|f32 complex|real|qegt p<candidates per wavefront trip>". */
+enum { MCLE_CODEBOOK_COMPLEX = 0, MCLE_CODEBOOK_REAL = 1, MCLE_CODEBOOK_QEGT = 2 };
+typedef struct mcle_codebook_cfg {
+    int32_t K, Nt, Ns, type;
+} mcle_codebook_cfg;
+typedef struct mcle_codebook_result {
+    uint64_t best_index;
+    double best_min_d2;
+    int32_t pair[2];
+    uint64_t n_candidates;
+} mcle_codebook_result;
+int mcle_chordal_min_dist(mcle_ctx* ctx, int dtype, const void* d_codebooks, size_t n_codebooks, int K, int Nt, int Ns,
+                          double* d_min_d2, int32_t* d_pair, double* d_d2);
+int mcle_codebook_generate(mcle_ctx* ctx, int dtype, int type, int K, int Nt, int Ns, uint64_t seed, uint64_t first,
+                           uint64_t count, void* d_out);
+int mcle_run_codebook_search(mcle_ctx* ctx, int dtype, const mcle_codebook_cfg* cfg, uint64_t seed, uint64_t first,
+                             uint64_t count, mcle_codebook_result* out, double* d_min_d2, int32_t* d_pair);
 
 /* ---- same-seed parity mode: NumPy's legacy global RandomState replayed on the device -------
  * Realization r receives exactly what the reference draws after np.random.seed(seed_base + r)

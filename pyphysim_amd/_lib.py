@@ -20,7 +20,7 @@ STREAM_DATA, STREAM_NOISE, STREAM_CHAN, STREAM_PHASE = 0, 1, 2, 3
 OPTIONS = {"no_mfma": 0, "mfma_variant": 1, "grid_oversub": 2, "flat_wgs_per_cu": 3, "single_tdl": 4,
            "tdl_mfma_waves": 5, "jakes_direct": 6, "f64_generic": 7,
            "f64_threads": 8, "bd_runtime_solve": 9, "demod_nocert": 10, "f64_variant": 11, "f32_mfma": 12, "tdl_kernel": 13,
-           "mimo_tdl_kernel": 14, "walk_legacy": 15, "staged_generic": 16}
+           "mimo_tdl_kernel": 14, "walk_legacy": 15, "staged_generic": 16, "codebook_no_pack": 17}
 
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 # MCLE_LIBRARY: another build of the same library (A/B runs of two builds on one box, scripts/experiments/)
@@ -142,6 +142,17 @@ class PilotMseCfg(Structure):
                 ("d_pilots", c_void_p), ("chan_factor", POINTER(c_double)), ("cov", POINTER(c_double))]
 
 
+class CodebookCfg(Structure):
+    _fields_ = [("K", c_int32), ("Nt", c_int32), ("Ns", c_int32), ("type", c_int32)]
+
+
+class CodebookResult(Structure):
+    _fields_ = [("best_index", c_uint64), ("best_min_d2", c_double), ("pair", c_int32 * 2), ("n_candidates", c_uint64)]
+
+
+CODEBOOK_TYPES = {"complex": 0, "real": 1, "qegt": 2}
+
+
 class LegacySeg(Structure):
     _fields_ = [("kind", c_int32), ("n", c_int32), ("range", c_uint32), ("reserved", c_uint32)]
 
@@ -249,6 +260,10 @@ _PROTOS = {
     "mcle_ls_estimate": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_size_t, _P]),
     "mcle_mmse_estimate": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, c_size_t, c_double, POINTER(c_double), _P]),
     "mcle_run_pilot_mse": (c_int, [_P, c_int, POINTER(PilotMseCfg), c_uint64, c_uint64, c_uint64, _P, _P, _P]),
+    "mcle_chordal_min_dist": (c_int, [_P, c_int, _P, c_size_t, c_int, c_int, c_int, _P, _P, _P]),
+    "mcle_codebook_generate": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_uint64, c_uint64, c_uint64, _P]),
+    "mcle_run_codebook_search": (c_int, [_P, c_int, POINTER(CodebookCfg), c_uint64, c_uint64, c_uint64, POINTER(CodebookResult),
+                                         _P, _P]),
     "mcle_legacy_draws": (c_int, [_P, POINTER(LegacySeg), c_int, c_uint32, c_uint64, c_uint64, _P, c_size_t, _P,
                                   c_size_t, _P]),
     "mcle_complex_from_parts": (c_int, [_P, c_int, _P, _P, c_double, _P, c_size_t]),

@@ -161,7 +161,7 @@ class Engine:
     # ---- kernel-selection options (mcle_ctx_set_option: per context, never read from the environment) ----
     def set_option(self, name, value):
         """name: a key of _lib.OPTIONS ('no_mfma', 'mfma_variant', 'grid_oversub', 'flat_wgs_per_cu', 'single_tdl',
-        'tdl_mfma_waves', 'jakes_direct', 'f64_generic', 'f64_threads', 'bd_runtime_solve', 'demod_nocert', 'f64_variant', 'f32_mfma', 'tdl_kernel', 'mimo_tdl_kernel', 'walk_legacy':
+        'tdl_mfma_waves', 'jakes_direct', 'f64_generic', 'f64_threads', 'bd_runtime_solve', 'demod_nocert', 'f64_variant', 'f32_mfma', 'tdl_kernel', 'mimo_tdl_kernel', 'walk_legacy', 'staged_generic', 'codebook_no_pack':
         include/mcle.h MCLE_OPT_* says what each selects); 0 restores the default."""
         if name not in _lib.OPTIONS:
             raise ValueError("unknown option %r (known: %s)" % (name, ", ".join(sorted(_lib.OPTIONS))))
@@ -1292,6 +1292,49 @@ class Engine:
         tot = [None if a is None else (float(np.cumsum(a)[-1]) if count else 0.0) for a in arrs]
         res = {"n_realizations": int(count), "err_ls": tot[0], "err_mmse": tot[1], "pow": tot[2]}
         return (res, arrs[0], arrs[1], arrs[2]) if per_realization else res
+
+    # ---- Grassmannian codebooks (csrc/kernels_codebook.hip) -------------------------------------------
+    def chordal_min_dist(self, codebooks, dtype=None, full=False):
+        """Squared chordal distances of codebooks [n, K, Nt, Ns] (or one [K, Nt, Ns]) (mcle_chordal_min_dist): returns
+        (min_d2 [n] float64, pair [n, 2] int32), with full=True also the symmetric d^2 matrices [n, K, K]; the leading axis
+        is dropped for a single codebook."""
+        dt = self._dt(dtype)
+        d_cb, _ = self._cin(codebooks, dt)
+        single = len(d_cb.shape) == 3
+        if len(d_cb.shape) not in (3, 4):
+            raise ValueError("codebooks must be [n, K, Nt, Ns] or [K, Nt, Ns] (got %s)" % (d_cb.shape,))
+        n = 1 if single else int(d_cb.shape[0])
+        K, Nt, Ns = (int(v) for v in d_cb.shape[-3:])
+        md2, pair = self.empty(n, np.float64), self.empty((n, 2), np.int32)
+        d2 = self.empty((n, K, K), np.float64) if full else None
+        self._raise_value(self.lib.mcle_chordal_min_dist(self.ctx, dt, d_cb.ptr, n, K, Nt, Ns, md2.ptr, pair.ptr,
+                                                         d2.ptr if full else None))
+        out = [md2.get(), pair.get()] + ([d2.get()] if full else [])
+        return tuple(v[0] for v in out) if single else tuple(out)
+
+    def codebook_generate(self, K, Nt, Ns, seed, first, count, codebook_type="complex", dtype=None, device=False):
+        """The search's candidates [first, first + count) of `seed` as they are before orthonormalisation
+        (mcle_codebook_generate): [count, K, Nt, Ns] complex."""
+        dt = self._dt(dtype)
+        out = self.empty((count, K, Nt, Ns), _lib.np_complex(dt))
+        self._raise_value(self.lib.mcle_codebook_generate(self.ctx, dt, int(_lib.CODEBOOK_TYPES.get(codebook_type, codebook_type)),
+                                                          int(K), int(Nt), int(Ns), int(seed), int(first), int(count), out.ptr))
+        return out if device else out.get()
+
+    def run_codebook_search(self, K, Nt, Ns, seed, first, count, codebook_type="complex", dtype=None, per_candidate=False):
+        """Fused random codebook search over the candidates [first, first + count) (mcle_run_codebook_search).  Returns
+        dict(best_index, best_min_d2, pair, n_candidates); with per_candidate=True also min_d2 [count] and pair [count, 2]."""
+        dt = self._dt(dtype)
+        cfg = _lib.CodebookCfg(int(K), int(Nt), int(Ns), int(_lib.CODEBOOK_TYPES.get(codebook_type, codebook_type)))
+        res = _lib.CodebookResult()
+        md2 = self.empty(count, np.float64) if per_candidate else None
+        pair = self.empty((count, 2), np.int32) if per_candidate else None
+        self._raise_value(self.lib.mcle_run_codebook_search(self.ctx, dt, byref(cfg), int(seed), int(first), int(count), byref(res),
+                                                            md2.ptr if per_candidate else None,
+                                                            pair.ptr if per_candidate else None))
+        out = {"best_index": int(res.best_index), "best_min_d2": float(res.best_min_d2),
+               "pair": (int(res.pair[0]), int(res.pair[1])), "n_candidates": int(res.n_candidates)}
+        return (out, md2.get(), pair.get()) if per_candidate else out
 
     # ---- same-seed parity mode (NumPy legacy RandomState on the device) ----------------------
     def legacy_draws(self, program, seed_base, first, count):
