@@ -509,12 +509,20 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
             //      the matrix cores, decisions ----
             if constexpr (!(ABL & 1024)) {
                 const int ln = opaque(lane);
-                const int g = ln & 15;
+                // W_N^(m kp), kp = kp0 + 16 uu: table m is ONE lane offset 16 m kp0 bytes behind the (scalar) table pointer and uu only moves
+                // the load's immediate, 16 sizeof(entry) m uu = 256 m uu < 4 096 bytes -- left to itself the compiler saw g + 16 (...) as an `or` and rebuilt
+                // every one of the addresses in 64 bits (round 15; the same loads, the same values)
+                const uint32_t kp0 = (uint32_t)opaque((ln & 15) + 16 * UU * j);
+                constexpr uint32_t kTwBytes = (uint32_t)sizeof(cx<T>);            // one table entry; 16 entries from uu to uu + 1
+                static_assert(16 * kTwBytes * (NW - 1) * (UU - 1) < 4096, "the load's immediate offset");
+                auto tw_at = [&](int m, int uu) {
+                    const char* lane_base = reinterpret_cast<const char*>(g_tw) + (size_t)(kTwBytes * (uint32_t)m * kp0);
+                    return *reinterpret_cast<const cx<T>*>(lane_base + 16 * (int)kTwBytes * m * uu);
+                };
 #pragma unroll
                 for (int uu = 0; uu < UU; ++uu) {
-                    const int kp = g + 16 * (UU * j + uu);
                     if constexpr (NW == 4) {
-                        const cx<T> w1 = g_tw[kp], w2 = g_tw[2 * kp], w3 = g_tw[3 * kp];
+                        const cx<T> w1 = tw_at(1, uu), w2 = tw_at(2, uu), w3 = tw_at(3, uu);
                         const cx<T> u0 = mk<T>(er[0][uu], ei[0][uu]);
                         const cx<T> u1 = cmul(mk<T>(er[1][uu], ei[1][uu]), w1);
                         const cx<T> u2 = cmul(mk<T>(er[2][uu], ei[2][uu]), w2);
@@ -526,7 +534,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                         cx<T> x[8];
                         x[0] = mk<T>(er[0][uu], ei[0][uu]);
 #pragma unroll
-                        for (int jj = 1; jj < 8; ++jj) x[jj] = cmul(mk<T>(er[jj][uu], ei[jj][uu]), g_tw[jj * kp]);
+                        for (int jj = 1; jj < 8; ++jj) x[jj] = cmul(mk<T>(er[jj][uu], ei[jj][uu]), tw_at(jj, uu));
                         cx<T> E[4], O[4];
                         CxOps<T>::template bfly4<false>(x[0], x[2], x[4], x[6], E[0], E[1], E[2], E[3]);
                         CxOps<T>::template bfly4<false>(x[1], x[3], x[5], x[7], O[0], O[1], O[2], O[3]);
@@ -541,7 +549,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                         v[8 * uu + 3] = cadd(E[3], t3); v[8 * uu + 7] = csub(E[3], t3);
                     } else {
                         const cx<T> u0 = mk<T>(er[0][uu], ei[0][uu]);
-                        const cx<T> u1 = cmul(mk<T>(er[1][uu], ei[1][uu]), g_tw[kp]);
+                        const cx<T> u1 = cmul(mk<T>(er[1][uu], ei[1][uu]), tw_at(1, uu));
                         v[2 * uu] = cadd(u0, u1);
                         v[2 * uu + 1] = csub(u0, u1);
                     }
@@ -556,17 +564,29 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                 if constexpr (!TD && !(ABL & 256)) {
                     const cx<T> hA = s_H[(ln & 3) * NT + (ln >> 4)];               // H[h mod 4][a]
                     const T hre = hA.x, him = hA.y, nhim = -hA.y;
+                    // by groups of four (round 15): four look-ups into four registers, then the sixteen products, first products first
+                    // -- the table reads stay ahead of the products that take them instead of one read, one wait, four products
 #pragma unroll
-                    for (int u = 0; u < 16; ++u) {
-                        const uint32_t lb = (wds[u >> 2] >> (8 * (u & 3))) & 0xFFu;
-                        cx<T> X;
-                        if constexpr (ABL & 32) X = mk<T>((T)lb, 1.0);
-                        else X = s_txtab[lb];
-                        T yr = __builtin_amdgcn_mfma_f64_4x4x4f64(hre, X.x, v[u].x, 0, 0, 0);
-                        T yi = __builtin_amdgcn_mfma_f64_4x4x4f64(him, X.x, v[u].y, 0, 0, 0);
-                        yr = __builtin_amdgcn_mfma_f64_4x4x4f64(nhim, X.y, yr, 0, 0, 0);
-                        yi = __builtin_amdgcn_mfma_f64_4x4x4f64(hre, X.y, yi, 0, 0, 0);
-                        v[u] = mk<T>(yr, yi);
+                    for (int i = 0; i < 4; ++i) {
+                        cx<T> X[4];
+#pragma unroll
+                        for (int jj = 0; jj < 4; ++jj) {
+                            const uint32_t lb = (wds[i] >> (8 * jj)) & 0xFFu;
+                            if constexpr (ABL & 32) X[jj] = mk<T>((T)lb, 1.0);
+                            else X[jj] = s_txtab[lb];
+                        }
+                        T yr[4], yi[4];
+#pragma unroll
+                        for (int jj = 0; jj < 4; ++jj) {
+                            yr[jj] = __builtin_amdgcn_mfma_f64_4x4x4f64(hre, X[jj].x, v[4 * i + jj].x, 0, 0, 0);
+                            yi[jj] = __builtin_amdgcn_mfma_f64_4x4x4f64(him, X[jj].x, v[4 * i + jj].y, 0, 0, 0);
+                        }
+#pragma unroll
+                        for (int jj = 0; jj < 4; ++jj) {
+                            yr[jj] = __builtin_amdgcn_mfma_f64_4x4x4f64(nhim, X[jj].y, yr[jj], 0, 0, 0);
+                            yi[jj] = __builtin_amdgcn_mfma_f64_4x4x4f64(hre, X[jj].y, yi[jj], 0, 0, 0);
+                            v[4 * i + jj] = mk<T>(yr[jj], yi[jj]);
+                        }
                     }
                 }
                 if constexpr (!(ABL & 1024)) {

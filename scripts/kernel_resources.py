@@ -8,6 +8,8 @@ record cannot corroborate occupancy claims; this file can.  Dynamic LDS is added
 (run_*_impl in csrc/*.hip) and is listed in DESIGN.md.
 
 usage: python scripts/kernel_resources.py r05      (after `make -C pyphysim_amd/csrc`: reads the built *.o files)
+       python scripts/kernel_resources.py r15 k_run_mimo_ofdm_pw     (only the kernels whose name contains the second argument:
+                                                                      a round that changed one family records that family)
 """
 import json
 import os
@@ -78,6 +80,7 @@ def waves_per_simd(vgpr, agpr):
 def main():
     import glob
     rnd = sys.argv[1] if len(sys.argv) > 1 else "r05"
+    only = sys.argv[2] if len(sys.argv) > 2 else ""
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
         for obj in sorted(glob.glob(os.path.join(CSRC, "*.o"))):
@@ -99,7 +102,7 @@ def main():
                 demangled = subprocess.run(["c++filt", name], capture_output=True,
                                            text=True).stdout.strip()
                 short = demangled.split("(")[0].replace("void mcle::", "")
-                if not short.startswith(PREFIXES):
+                if not short.startswith(PREFIXES) or only not in short:
                     continue
                 rec = {}
                 for k in KEYS:
@@ -114,7 +117,7 @@ def main():
     os.makedirs(dst, exist_ok=True)
     spilled = {k: v["vgpr_spill_count"] for k, v in sorted(out.items()) if v["default"] and v.get("vgpr_spill_count")}
     doc = {"_source": "code-object metadata of the in-tree build (llvm-objcopy .hip_fatbin + clang-offload-bundler + llvm-readelf "
-                      "--notes), gfx950, flags of pyphysim_amd/csrc/Makefile",
+                      "--notes), gfx950, flags of pyphysim_amd/csrc/Makefile" + ("; only kernels named *%s*" % only if only else ""),
            "_default": "\"default\": true = what the dispatchers pick with every option at 0 (scripts/kernel_resources.py DEFAULT)",
            "_default_kernels_with_spilled_vgprs": spilled,
            "kernels": dict(sorted(out.items()))}
