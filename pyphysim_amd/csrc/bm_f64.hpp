@@ -41,25 +41,42 @@
 #define MCLE_BM_RINT(a) __builtin_rint(a)
 #endif
 
+// the two bit-field operations of bm_neg_log_q: one instruction each on the device, the plain C++ they stand for in a host build
+#ifndef MCLE_BM_ALIGNBIT                                                       // low 32 bits of (hi:lo) >> s, 0 <= s < 32
+#ifdef __HIPCC__
+#define MCLE_BM_ALIGNBIT(hi, lo, s) __builtin_amdgcn_alignbit(hi, lo, s)
+#else
+#define MCLE_BM_ALIGNBIT(hi, lo, s) ((uint32_t)(((((uint64_t)(hi)) << 32) | (uint64_t)(uint32_t)(lo)) >> (s)))
+#endif
+#endif
+#ifndef MCLE_BM_SBFE                                                           // bits [off, off + width) of x, sign-extended
+#ifdef __HIPCC__
+#define MCLE_BM_SBFE(x, off, width) __builtin_amdgcn_sbfe(x, off, width)
+#else
+#define MCLE_BM_SBFE(x, off, width) ((int32_t)((uint32_t)(x) << (32 - (off) - (width))) >> (32 - (width)))
+#endif
+#endif
+
 #include "bm_tables.hpp"
 
 namespace mcle {
 
 constexpr int kBmLogLen = 65 * 2, kBmThetaLen = 129, kBmTrigLen = 129 * 2;     // doubles: 4.1 KiB in all
 
-// A kernel's own LDS copy of the three tables, laid out [kBmLog | kBmTheta | kBmTrig] (call before a barrier)
+// A kernel's own LDS copy of the three tables, laid out [kBmLogQ | kBmTheta | kBmTrig] (call before a barrier).  The log slot holds
+// the table of bm_neg_log_q, the form every sample is drawn with; kBmLog (bm_neg_log, its witness) has no LDS copy.
 constexpr int kBmLdsDoubles = kBmLogLen + kBmThetaLen + kBmTrigLen;
 #ifdef __HIPCC__
 __device__ __forceinline__ void bm_tables_to_lds(double* s_bm, int tid, int nthreads) {
-    for (int i = tid; i < kBmLogLen; i += nthreads) s_bm[i] = kBmLog[i];
+    for (int i = tid; i < kBmLogLen; i += nthreads) s_bm[i] = kBmLogQ[i];
     for (int i = tid; i < kBmThetaLen; i += nthreads) s_bm[kBmLogLen + i] = kBmTheta[i];
     for (int i = tid; i < kBmTrigLen; i += nthreads) s_bm[kBmLogLen + kBmThetaLen + i] = kBmTrig[i];
 }
-// The same tables laid out [kBmLog | kBmTrig | kBmTheta]: kBmLogLen is even, so BOTH pair tables start on a 16-byte boundary of a
+// The same tables laid out [kBmLogQ | kBmTrig | kBmTheta]: kBmLogLen is even, so BOTH pair tables start on a 16-byte boundary of a
 // 16-byte aligned copy and a sample's (1 / c_j, ln c_j) and (cos, sin) are one 16-byte read each (PAIR = true below)
 __device__ __forceinline__ void bm_tables_to_lds_pairs(double* s_bm, int tid, int nthreads) {
     static_assert(kBmLogLen % 2 == 0, "the trig pairs start on a 16-byte boundary");
-    for (int i = tid; i < kBmLogLen; i += nthreads) s_bm[i] = kBmLog[i];
+    for (int i = tid; i < kBmLogLen; i += nthreads) s_bm[i] = kBmLogQ[i];
     for (int i = tid; i < kBmTrigLen; i += nthreads) s_bm[kBmLogLen + i] = kBmTrig[i];
     for (int i = tid; i < kBmThetaLen; i += nthreads) s_bm[kBmLogLen + kBmTrigLen + i] = kBmTheta[i];
 }
@@ -102,6 +119,45 @@ MCLE_BM_FN double bm_neg_log(uint32_t x0, const double* tlog = kBmLog) {
     return -(big + small);
 }
 
+// The same value, word for word, with the argument reduction in integer arithmetic.  ud = x0 + 0.5 has a 33-bit odd significand,
+// so the fraction of its mantissa is a 32-bit integer f (bits 51 .. 20 of the double) and m = 1 + f 2^-32.  Node j is f rounded to a
+// multiple of 2^26, hence m - c_j = d 2^-32 EXACTLY (d 2^-33 for a folded node, j >= 32) with d = the low 26 bits of f, sign-extended,
+// |d| <= 2^25.  kBmLogQ holds fl(1 / c_j) times that power of two, and a power-of-two scale commutes with the one rounding of the
+// product: r = fl((double)d * kBmLogQ[2 j]) is the double bm_neg_log's fl((m - c) * inv_c) is, and everything behind r is the same
+// code.  Neither m nor c is assembled: 8 integer instructions + cvt, cvt, add in front of the product, against 14 + cvt, add, add.
+// (tests/test_bm_logq_cpu.py: bit-identical on 1.7e7 chosen and random words; tests/test_gpu_bm_logq.py: the same on the device.)
+template <bool PAIR = false>
+MCLE_BM_FN double bm_neg_log_q(uint32_t x0, const double* tlogq = kBmLogQ) {
+    const double ud = (double)x0 + 0.5;                                   // exact: u 2^32
+    const uint64_t bits = __builtin_bit_cast(uint64_t, ud);
+    const uint32_t hi = (uint32_t)(bits >> 32);
+    const uint32_t f = MCLE_BM_ALIGNBIT(hi, (uint32_t)bits, 20);          // the mantissa's fraction, 32 bits
+    const int d = MCLE_BM_SBFE((int)f, 0, 26);                            // f - j 2^26
+    // nearest node: j >= 32 <=> the top 20 mantissa bits + 0x2000 reach 0x80000, so adding 0x82000 to the high word carries the fold
+    // into the exponent field
+    const int e = (int)(hi + 0x82000u - ((1023u + 32u) << 20)) >> 20;
+    const uint32_t off = (((f >> 1) + (1u << 24)) >> 21) & 0x7F0u;        // 16 j (bytes), j = (f + 2^25) >> 26 = 0 .. 64
+    const char* entry = reinterpret_cast<const char*>(tlogq) + off;
+    double inv_cq, lnc;
+    if constexpr (PAIR) {
+        const BmPair t = *reinterpret_cast<const BmPair*>(entry);
+        inv_cq = t[0];
+        lnc = t[1];
+    } else {
+        inv_cq = reinterpret_cast<const double*>(entry)[0];
+        lnc = reinterpret_cast<const double*>(entry)[1];
+    }
+    const double r = (double)d * inv_cq;
+    const double r2 = r * r;
+    const double a0 = MCLE_BM_FMA(r, 1.0 / 3.0, -0.5);
+    const double a1 = MCLE_BM_FMA(r, 0.2, -0.25);
+    const double a2 = MCLE_BM_FMA(r, 1.0 / 7.0, -1.0 / 6.0);
+    const double q = MCLE_BM_FMA(r2, MCLE_BM_FMA(r2, a2, a1), a0);
+    const double small = MCLE_BM_FMA(r2, q, r);
+    const double big = MCLE_BM_FMA((double)e, 0x1.62e42fefa39efp-1, lnc);    // e ln 2 + ln c_j, one rounding
+    return -(big + small);
+}
+
 // sqrt(a), a in [2e-10, 23]
 MCLE_BM_FN double bm_sqrt(double a) {
     const double y = MCLE_BM_RSQ(a);
@@ -119,17 +175,20 @@ MCLE_BM_FN double bm_sqrt(double a) {
 template <bool PAIR = false>
 MCLE_BM_FN void bm_sincos(uint32_t x1, double& c, double& s, const double* ttheta = kBmTheta, const double* ttrig = kBmTrig) {
     const double ang = (double)x1 * 0x1.921fb54442d18p-30;                // (2 pi_d) 2^-32: fl(.) == NumPy's 2.0*np.pi*(x1*2**-32)
-    const uint32_t k = ((x1 >> 24) + 1u) >> 1;                            // nearest node, 0 .. 128
+    // nearest node k = ((x1 >> 24) + 1) >> 1 = 0 .. 128 as the byte offset 16 k of its {cos, sin} pair; theta_k sits at half of it (four
+    // instructions for the two addresses instead of five: the compiler does not see that 8 k is 16 k shifted)
+    const uint32_t off = ((x1 >> 21) + 8u) & 0xFF0u;
+    const char* entry = reinterpret_cast<const char*>(ttrig) + off;
     double ct, st;
     if constexpr (PAIR) {
-        const BmPair t = *reinterpret_cast<const BmPair*>(ttrig + 2 * k);
+        const BmPair t = *reinterpret_cast<const BmPair*>(entry);
         ct = t[0];
         st = t[1];
     } else {
-        ct = ttrig[2 * k];
-        st = ttrig[2 * k + 1];
+        ct = reinterpret_cast<const double*>(entry)[0];
+        st = reinterpret_cast<const double*>(entry)[1];
     }
-    const double r = ang - ttheta[k];                                     // exact
+    const double r = ang - *reinterpret_cast<const double*>(reinterpret_cast<const char*>(ttheta) + (off >> 1));    // exact
     const double s2 = r * r;
     double p = MCLE_BM_FMA(s2, -1.0 / 5040.0, 1.0 / 120.0);
     p = MCLE_BM_FMA(s2, p, -1.0 / 6.0);

@@ -79,7 +79,7 @@ __device__ __forceinline__ float2 cn_from_words(uint32_t x0, uint32_t x1, float 
 // complex128: the table + polynomial forms of bm_f64.hpp (within one unit in the last place of the device libm's
 // log / sincos / sqrt this replaced, at a quarter of the instructions)
 __device__ __forceinline__ double2 cn_from_words(uint32_t x0, uint32_t x1, double sigma) {
-    const double rad = sigma * bm_sqrt(bm_neg_log(x0));
+    const double rad = sigma * bm_sqrt(bm_neg_log_q(x0));
     double s, c;
     bm_sincos(x1, c, s);
     double2 z;
@@ -90,7 +90,7 @@ __device__ __forceinline__ double2 cn_from_words(uint32_t x0, uint32_t x1, doubl
 
 // the same with the tables of bm_f64.hpp read from the caller's LDS copy (bm_tables_to_lds)
 __device__ __forceinline__ double2 cn_from_words_lds(uint32_t x0, uint32_t x1, double sigma, const double* s_bm) {
-    const double rad = sigma * bm_sqrt(bm_neg_log(x0, s_bm));
+    const double rad = sigma * bm_sqrt(bm_neg_log_q(x0, s_bm));
     double s, c;
     bm_sincos(x1, c, s, s_bm + kBmLogLen, s_bm + kBmLogLen + kBmThetaLen);
     double2 z;
@@ -101,7 +101,7 @@ __device__ __forceinline__ double2 cn_from_words_lds(uint32_t x0, uint32_t x1, d
 
 // the same from a copy laid out by bm_tables_to_lds_pairs (16-byte aligned): three LDS reads per sample instead of five, same values
 __device__ __forceinline__ double2 cn_from_words_lds_pairs(uint32_t x0, uint32_t x1, double sigma, const double* s_bm) {
-    const double rad = sigma * bm_sqrt(bm_neg_log<true>(x0, s_bm));
+    const double rad = sigma * bm_sqrt(bm_neg_log_q<true>(x0, s_bm));
     double s, c;
     bm_sincos<true>(x1, c, s, s_bm + kBmLogLen + kBmTrigLen, s_bm + kBmLogLen);
     double2 z;
