@@ -200,6 +200,69 @@ MCLE_BM_FN void bm_sincos(uint32_t x1, double& c, double& s, const double* tthet
     s = st + MCLE_BM_FMA(ct, sr, st * cm);
 }
 
+// ---- the sample in two phases ----
+// bm_neg_log_q<true>, bm_sqrt and bm_sincos<true> cut where their table values arrive.  The FETCH phase does the integer work in
+// front of the three table reads and ends with the reads issued: nothing in it takes a table value, so a caller that fetches sample
+// n + 1 before it finishes sample n (pipeline_mimo_pw.hip) has a whole sample's arithmetic between a read and the wait that covers it
+// instead of the five instructions of the one-phase form.  The FINISH phase is every floating-point expression of the one-phase
+// functions, operand for operand -- the two conversions included, so ang = (double)x1 * C sits next to ang - theta_k and contracts
+// with it exactly as it does in bm_sincos.  The record holds the integer parts (three registers), not their doubles (six).
+// tests/test_bm_phase_cpu.py: fetch + finish against the one-phase sample as 64-bit words; tests/test_gpu_bm_phase.py: the same on
+// the device, where contraction is on.
+struct BmFetched {
+    int d, e;                  // bm_neg_log_q: the residual's integer numerator and the exponent (fold included)
+    uint32_t x1;               // the angle word
+    BmPair lg;                 // {fl(1 / c_j) 2^-32 [2^-33], ln c_j}
+    BmPair cs;                 // {cos theta_k, sin theta_k}
+    double theta;              // theta_k
+};
+
+// tlogq / ttrig: 16-byte aligned pair tables (bm_tables_to_lds_pairs), ttheta: the node angles
+MCLE_BM_FN BmFetched bm_sample_fetch(uint32_t x0, uint32_t x1, const double* tlogq, const double* ttheta, const double* ttrig) {
+    BmFetched t;
+    const double ud = (double)x0 + 0.5;
+    const uint64_t bits = __builtin_bit_cast(uint64_t, ud);
+    const uint32_t hi = (uint32_t)(bits >> 32);
+    const uint32_t f = MCLE_BM_ALIGNBIT(hi, (uint32_t)bits, 20);
+    t.d = MCLE_BM_SBFE((int)f, 0, 26);
+    t.e = (int)(hi + 0x82000u - ((1023u + 32u) << 20)) >> 20;
+    const uint32_t offl = (((f >> 1) + (1u << 24)) >> 21) & 0x7F0u;
+    t.lg = *reinterpret_cast<const BmPair*>(reinterpret_cast<const char*>(tlogq) + offl);
+    t.x1 = x1;
+    const uint32_t offt = ((x1 >> 21) + 8u) & 0xFF0u;
+    t.cs = *reinterpret_cast<const BmPair*>(reinterpret_cast<const char*>(ttrig) + offt);
+    t.theta = *reinterpret_cast<const double*>(reinterpret_cast<const char*>(ttheta) + (offt >> 1));
+    return t;
+}
+
+// sigma sqrt(-ln u) (cos, sin): the expressions of bm_neg_log_q, bm_sqrt, bm_sincos and of the product that closes the sample
+MCLE_BM_FN void bm_sample_finish(const BmFetched& t, double sigma, double& re, double& im) {
+    const double inv_cq = t.lg[0], lnc = t.lg[1];
+    const double r = (double)t.d * inv_cq;
+    const double r2 = r * r;
+    const double a0 = MCLE_BM_FMA(r, 1.0 / 3.0, -0.5);
+    const double a1 = MCLE_BM_FMA(r, 0.2, -0.25);
+    const double a2 = MCLE_BM_FMA(r, 1.0 / 7.0, -1.0 / 6.0);
+    const double q = MCLE_BM_FMA(r2, MCLE_BM_FMA(r2, a2, a1), a0);
+    const double small = MCLE_BM_FMA(r2, q, r);
+    const double big = MCLE_BM_FMA((double)t.e, 0x1.62e42fefa39efp-1, lnc);
+    const double rad = sigma * bm_sqrt(-(big + small));
+    const double ang = (double)t.x1 * 0x1.921fb54442d18p-30;
+    const double ct = t.cs[0], st = t.cs[1];
+    const double rr = ang - t.theta;
+    const double s2 = rr * rr;
+    double p = MCLE_BM_FMA(s2, -1.0 / 5040.0, 1.0 / 120.0);
+    p = MCLE_BM_FMA(s2, p, -1.0 / 6.0);
+    const double sr = MCLE_BM_FMA(rr * s2, p, rr);
+    double qq = MCLE_BM_FMA(s2, -1.0 / 720.0, 1.0 / 24.0);
+    qq = MCLE_BM_FMA(s2, qq, -0.5);
+    const double cm = s2 * qq;
+    const double c = ct + MCLE_BM_FMA(-st, sr, ct * cm);
+    const double s = st + MCLE_BM_FMA(ct, sr, st * cm);
+    re = rad * c;
+    im = rad * s;
+}
+
 // The same with the node angle and its cos / sin in ONE 32-byte entry {cos, sin, theta, -} (a kernel's own LDS copy, built by
 // bm_trig_packed_to_lds): one address for both reads of a sample (variant measured in round 4, pipeline_mimo_planar.hip)
 MCLE_BM_FN void bm_sincos_packed(uint32_t x1, double& c, double& s, const double* tpk) {

@@ -110,6 +110,17 @@ __device__ __forceinline__ double2 cn_from_words_lds_pairs(uint32_t x0, uint32_t
     return z;
 }
 
+// cn_from_words_lds_pairs in two phases (bm_f64.hpp: bm_sample_fetch / bm_sample_finish): the fetch ends with the sample's three LDS
+// reads issued, the finish is the arithmetic -- same words, same tables, same values; cn_from_words_lds_pairs stays the witness
+__device__ __forceinline__ BmFetched cn_fetch_lds_pairs(uint32_t x0, uint32_t x1, const double* s_bm) {
+    return bm_sample_fetch(x0, x1, s_bm, s_bm + kBmLogLen + kBmTrigLen, s_bm + kBmLogLen);
+}
+__device__ __forceinline__ double2 cn_finish(const BmFetched& t, double sigma) {
+    double2 z;
+    bm_sample_finish(t, sigma, z.x, z.y);
+    return z;
+}
+
 // complex sample i of (stream): one Philox call, half of it used
 template <typename T>
 __device__ __forceinline__ cx<T> cn_sample(const Rng& rng, uint32_t stream, uint64_t i, T sigma) {

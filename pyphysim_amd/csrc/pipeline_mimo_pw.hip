@@ -262,6 +262,11 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
         unsigned se = 0, be = 0;
         for (int os = 0; os < pp.n_ofdm_sym; ++os) {
             if (it > 0 || os > 0) __syncthreads();          // B5: the previous symbol's exchange planes and labels have been read
+            // The loop comes back here with scalar loads of the decode on the books, and a scalar load returns out of order: the first
+            // LDS wait behind it can only be lgkmcnt(0), which in the pipelined draw would wait for block 1's table reads three
+            // instructions behind their issue.  Retire them here, behind the barrier, where nothing is in flight: the draw's first wait
+            // is then a counted one like the others (s_waitcnt lgkmcnt(0) alone: vmcnt and expcnt fields at their maxima).
+            if constexpr (ROWS && !(ABL & 128)) __builtin_amdgcn_s_waitcnt(0xC07F);
             // ---- S0a: this thread's DATA block: subcarriers d = 4 tid .. 4 tid + 3, four antennas each -> label bytes, laid out
             //      [antenna][group g = k' mod 16][q + NW u] for bin k = k' + 256 q, k' = g + 16 u (full band: k = d ^ (N / 2)) ----
             {
@@ -407,19 +412,40 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                 const int f = 4 * j + rho, ant = f >> kLogNW, cls = f & (NW - 1);
                 const uint64_t i00 = (uint64_t)ant * row + (uint64_t)os * (N + cp) + cp + (cls & ~1) + 32 * NW * (rho & 1) + NW * (uint64_t)pw_mtime(h, 0);
                 const uint32_t b0 = (uint32_t)(i00 >> 1);
+                if constexpr (ABL & 128) {
 #pragma unroll
-                for (int cc = 0; cc < 8; ++cc) {
-                    Words4 b;
-                    if constexpr (ABL & 128) b.w[0] = b.w[1] = b.w[2] = b.w[3] = b0 + cc;
-                    else b = rng.block(STREAM_NOISE, b0 + (uint32_t)(NW / 2) * (uint32_t)pw_mtime(0, cc));
-                    pw_row_swap(b.w[0], b.w[2]);
-                    pw_row_swap(b.w[1], b.w[3]);
-                    if constexpr (ABL & 128) {
+                    for (int cc = 0; cc < 8; ++cc) {
+                        Words4 b;
+                        b.w[0] = b.w[1] = b.w[2] = b.w[3] = b0 + cc;
+                        pw_row_swap(b.w[0], b.w[2]);
+                        pw_row_swap(b.w[1], b.w[3]);
                         v[cc] = mk<T>((T)b.w[0], sigma);
                         v[8 + cc] = mk<T>((T)b.w[2], sigma);
-                    } else {
-                        v[cc] = cn_from_words_lds_pairs(b.w[0], b.w[1], sigma, s_bm);
-                        v[8 + cc] = cn_from_words_lds_pairs(b.w[2], b.w[3], sigma, s_bm);
+                    }
+                } else {
+                    // Round 17: THE DRAW IS PIPELINED ONE BLOCK DEEP.  A sample's three table reads take their addresses from Philox words
+                    // and its arithmetic starts with their values: compiled sample after sample, every read was waited on in full about
+                    // five instructions behind its issue, forty times per realization, and the wavefront had nothing of its own to
+                    // cover it.  Block cc + 1 is FETCHED -- Philox, the two row swaps, the integer parts and the six reads of its two
+                    // samples (cn_fetch_lds_pairs) -- before block cc is FINISHED (cn_finish: the arithmetic of cn_from_words_lds_pairs,
+                    // word for word), and the scheduling barriers hold that order: a read is now a block's arithmetic ahead of the
+                    // counted wait that covers it.  Same words, same reads, same values, same registers v[cc], v[8 + cc].
+                    BmFetched ft[8][2];
+                    auto fetch = [&](int cc) {
+                        Words4 b = rng.block(STREAM_NOISE, b0 + (uint32_t)(NW / 2) * (uint32_t)pw_mtime(0, cc));
+                        pw_row_swap(b.w[0], b.w[2]);
+                        pw_row_swap(b.w[1], b.w[3]);
+                        ft[cc][0] = cn_fetch_lds_pairs(b.w[0], b.w[1], s_bm);
+                        ft[cc][1] = cn_fetch_lds_pairs(b.w[2], b.w[3], s_bm);
+                    };
+                    fetch(0);
+#pragma unroll
+                    for (int cc = 0; cc < 8; ++cc) {
+                        if (cc + 1 < 8) fetch(cc + 1);
+                        __builtin_amdgcn_sched_barrier(0);
+                        v[cc] = cn_finish(ft[cc][0], sigma);
+                        v[8 + cc] = cn_finish(ft[cc][1], sigma);
+                        __builtin_amdgcn_sched_barrier(0);
                     }
                 }
             }
@@ -479,6 +505,24 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
             // ---- the exchange: Y_j[k'] of receive antenna r (lane (r, g), register u: k' = g + 16 u) -> plane j at r 272 + k', re then
             //      im; lane (r, g) of wavefront jw reads the NW partial transforms of ITS k' = g + 16 (UU jw + uu), antenna r only ----
             T er[NW][UU], ei[NW][UU];
+            // Round 17 (default form by lane row): what the code behind B4 reads and the exchange does not write -- the lane's label
+            // row, H[h mod 4][a], G[h mod 4][r], the last stage's twiddles of uu = 0 -- is read BEFORE the wait at B4, so its latency
+            // runs while the wavefront stands at the barrier; the twiddles of uu + 1 are then issued ahead of the butterflies of uu.
+            // The same loads, the same values, another place.
+            constexpr bool kAhead = ROWS && ABL == 0;
+            constexpr uint32_t kTwBytes = (uint32_t)sizeof(cx<T>);                // one twiddle table entry; 16 entries from uu to uu + 1
+            uint32_t kp0 = 0;
+            // W_N^(m kp), kp = kp0 + 16 uu: table m is ONE lane offset 16 m kp0 bytes behind the (scalar) table pointer and uu only moves
+            // the load's immediate, 16 sizeof(entry) m uu = 256 m uu < 4 096 bytes -- left to itself the compiler saw g + 16 (...) as an `or` and rebuilt
+            // every one of the addresses in 64 bits (round 15; the same loads, the same values)
+            static_assert(16 * kTwBytes * (NW - 1) * (UU - 1) < 4096, "the load's immediate offset");
+            auto tw_at = [&](int m, int uu) {
+                const char* lane_base = reinterpret_cast<const char*>(g_tw) + (size_t)(kTwBytes * (uint32_t)m * kp0);
+                return *reinterpret_cast<const cx<T>*>(lane_base + 16 * (int)kTwBytes * m * uu);
+            };
+            cx<T> twb[2][NW - 1];                                                 // (kAhead) twiddles of uu in twb[uu & 1]
+            uint4 lab_ahead = make_uint4(0, 0, 0, 0);
+            cx<T> hA_ahead = mk<T>(0, 0), gA_ahead = mk<T>(0, 0);
             {
                 const int ln = opaque(lane);
                 const int r = ln >> 4, g = ln & 15;
@@ -499,6 +543,14 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                 __syncthreads();                               // B3
 #pragma unroll
                 for (int u = 0; u < 16; ++u) s_mine[wpos + 16 * u] = v[u].y;
+                if constexpr (kAhead) {
+                    kp0 = (uint32_t)opaque((ln & 15) + 16 * UU * j);
+#pragma unroll
+                    for (int m = 1; m < NW; ++m) twb[0][m - 1] = tw_at(m, 0);
+                    lab_ahead = *reinterpret_cast<const uint4*>(s_lab + ln * kLabStride + 16 * j);
+                    hA_ahead = s_H[(ln & 3) * NT + (ln >> 4)];
+                    gA_ahead = s_G[(ln & 3) * NR + (ln >> 4)];
+                }
                 __syncthreads();                               // B4
 #pragma unroll
                 for (int jj = 0; jj < NW; ++jj)
@@ -509,20 +561,23 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
             //      the matrix cores, decisions ----
             if constexpr (!(ABL & 1024)) {
                 const int ln = opaque(lane);
-                // W_N^(m kp), kp = kp0 + 16 uu: table m is ONE lane offset 16 m kp0 bytes behind the (scalar) table pointer and uu only moves
-                // the load's immediate, 16 sizeof(entry) m uu = 256 m uu < 4 096 bytes -- left to itself the compiler saw g + 16 (...) as an `or` and rebuilt
-                // every one of the addresses in 64 bits (round 15; the same loads, the same values)
-                const uint32_t kp0 = (uint32_t)opaque((ln & 15) + 16 * UU * j);
-                constexpr uint32_t kTwBytes = (uint32_t)sizeof(cx<T>);            // one table entry; 16 entries from uu to uu + 1
-                static_assert(16 * kTwBytes * (NW - 1) * (UU - 1) < 4096, "the load's immediate offset");
-                auto tw_at = [&](int m, int uu) {
-                    const char* lane_base = reinterpret_cast<const char*>(g_tw) + (size_t)(kTwBytes * (uint32_t)m * kp0);
-                    return *reinterpret_cast<const cx<T>*>(lane_base + 16 * (int)kTwBytes * m * uu);
+                if constexpr (!kAhead) kp0 = (uint32_t)opaque((ln & 15) + 16 * UU * j);
+                // kAhead: the twiddles of uu were loaded one step ahead (uu = 0: before B4), those of uu + 1 go out before the butterflies of uu
+                auto tw_of = [&](int m, int uu) {
+                    if constexpr (kAhead) return twb[uu & 1][m - 1];
+                    else return tw_at(m, uu);
                 };
 #pragma unroll
                 for (int uu = 0; uu < UU; ++uu) {
+                    if constexpr (kAhead) {
+                        if (uu + 1 < UU) {
+#pragma unroll
+                            for (int m = 1; m < NW; ++m) twb[(uu + 1) & 1][m - 1] = tw_at(m, uu + 1);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
                     if constexpr (NW == 4) {
-                        const cx<T> w1 = tw_at(1, uu), w2 = tw_at(2, uu), w3 = tw_at(3, uu);
+                        const cx<T> w1 = tw_of(1, uu), w2 = tw_of(2, uu), w3 = tw_of(3, uu);
                         const cx<T> u0 = mk<T>(er[0][uu], ei[0][uu]);
                         const cx<T> u1 = cmul(mk<T>(er[1][uu], ei[1][uu]), w1);
                         const cx<T> u2 = cmul(mk<T>(er[2][uu], ei[2][uu]), w2);
@@ -534,7 +589,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                         cx<T> x[8];
                         x[0] = mk<T>(er[0][uu], ei[0][uu]);
 #pragma unroll
-                        for (int jj = 1; jj < 8; ++jj) x[jj] = cmul(mk<T>(er[jj][uu], ei[jj][uu]), tw_at(jj, uu));
+                        for (int jj = 1; jj < 8; ++jj) x[jj] = cmul(mk<T>(er[jj][uu], ei[jj][uu]), tw_of(jj, uu));
                         cx<T> E[4], O[4];
                         CxOps<T>::template bfly4<false>(x[0], x[2], x[4], x[6], E[0], E[1], E[2], E[3]);
                         CxOps<T>::template bfly4<false>(x[1], x[3], x[5], x[7], O[0], O[1], O[2], O[3]);
@@ -549,7 +604,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                         v[8 * uu + 3] = cadd(E[3], t3); v[8 * uu + 7] = csub(E[3], t3);
                     } else {
                         const cx<T> u0 = mk<T>(er[0][uu], ei[0][uu]);
-                        const cx<T> u1 = cmul(mk<T>(er[1][uu], ei[1][uu]), tw_at(1, uu));
+                        const cx<T> u1 = cmul(mk<T>(er[1][uu], ei[1][uu]), tw_of(1, uu));
                         v[2 * uu] = cadd(u0, u1);
                         v[2 * uu + 1] = csub(u0, u1);
                     }
@@ -557,15 +612,21 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
             }
             {
                 const int ln = opaque(lane);
-                const uint4 L = *reinterpret_cast<const uint4*>(s_lab + ln * kLabStride + 16 * j);    // labels of my sixteen bins, stream a
+                uint4 L;                                                                               // labels of my sixteen bins, stream a
+                if constexpr (kAhead) L = lab_ahead;
+                else L = *reinterpret_cast<const uint4*>(s_lab + ln * kLabStride + 16 * j);
                 const uint32_t wds[4] = {L.x, L.y, L.z, L.w};
                 // default form: Y_r = sum_a H[r][a] X_a + noise spectrum -- byte q + NW uu of L is stream a's label at the bin of register
                 // q + NW uu, lane (a, g) supplies H[h mod 4][a] and its symbol, lane (r, g) the noise and takes Y_r
                 if constexpr (!TD && !(ABL & 256)) {
-                    const cx<T> hA = s_H[(ln & 3) * NT + (ln >> 4)];               // H[h mod 4][a]
+                    cx<T> hA;                                                      // H[h mod 4][a]
+                    if constexpr (kAhead) hA = hA_ahead;
+                    else hA = s_H[(ln & 3) * NT + (ln >> 4)];
                     const T hre = hA.x, him = hA.y, nhim = -hA.y;
                     // by groups of four (round 15): four look-ups into four registers, then the sixteen products, first products first
                     // -- the table reads stay ahead of the products that take them instead of one read, one wait, four products
+                    // (round 17: the look-ups of group i + 1 ahead of the products of group i cost a second set of sixteen registers here,
+                    // where the kernel's pressure peaks -- four spilled at the 168 bound: not in the build)
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         cx<T> X[4];
@@ -590,7 +651,9 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                     }
                 }
                 if constexpr (!(ABL & 1024)) {
-                const cx<T> gA = s_G[(ln & 3) * NR + (ln >> 4)];                   // G[h mod 4][r]
+                cx<T> gA;                                                          // G[h mod 4][r]
+                if constexpr (kAhead) gA = gA_ahead;
+                else gA = s_G[(ln & 3) * NR + (ln >> 4)];
                 const T gre = gA.x, gim = gA.y, ngim = -gA.y;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
