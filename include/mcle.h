@@ -839,8 +839,10 @@ int mcle_mmse_estimate(mcle_ctx* ctx, int dtype, const void* d_Y, const void* d_
  * d_err_ls, d_err_mmse, d_pow [count]: |h^_LS - h|_F^2, |h^_MMSE - h|_F^2, |h|_F^2 per realization, every entry written;
  * d_err_mmse may be NULL when cov is NULL.  They do not depend on the grid, on MCLE_OPT_GRID_OVERSUB or on how
  * [first, first + count) is split; the caller sums in index order.  count = 0 returns MCLE_OK and launches nothing.
- * Draws: DESIGN section 4 (pilot phases: stream 3, w: stream 2, noise: stream 1).  A shape whose working set does not
- * fit the 160 KiB of LDS is refused ("does not fit").
+ * Draws: DESIGN section 4 (pilot phases: stream 3, w: stream 2, noise: stream 1).  No shape inside the argument rules
+ * exceeds the 160 KiB of LDS: the largest working set of a wavefront is 133 120 bytes (nr = 128, nt = 8, n_pilots = 256,
+ * drawn pilots, MCLE_F64).  The launcher still checks the size ("does not fit"), but the argument rules make that refusal
+ * unreachable; it is a guard for the day a rule is widened.
  * mcle_ctx_last_kernel: "pilot_mse f64|f32 b<realizations per wavefront> ls|ls+mmse" (+ " gl": L applied from global memory). */
 typedef struct mcle_pilot_mse_cfg {
     int32_t nr, nt, n_pilots;           /* 1..128, 1..8, nt..256 */

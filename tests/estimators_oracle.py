@@ -137,3 +137,82 @@ def ledger_case(name):
         return default_cfg(nr=3, n_pilots=10, L=None, cov=0.49 * np.eye(3), **base)
     C0 = toeplitz_cov(16, 0.9)
     return default_cfg(nr=16, n_pilots=8, L=np.linalg.cholesky(C0), cov=0.49 * C0, **base)
+
+
+# ---- the shape envelope of the pipeline (tests/test_estimators_envelope_cpu.py, tests/test_gpu_estimators_envelope.py) ----
+ENVELOPE_SEED = 20261018
+ENVELOPE_COUNT = 37                     # tiles of 16: two and a tail of 5; of 8, 4 and 2: a tail of 5, 1 and 1
+ENVELOPE_FIRSTS = (0, 2 ** 32 - 5)      # the second range crosses 2^32 after five realizations
+
+
+def envelope_reals(first):
+    return np.arange(ENVELOPE_COUNT, dtype=np.uint64) + np.uint64(first)
+
+
+def dft_pilots(nt, P, power):
+    """The first nt rows of the P-point DFT matrix times sqrt(power): s s^H = P power I"""
+    return np.sqrt(power) * np.exp(-2j * np.pi * np.outer(np.arange(nt), np.arange(P)) / P)
+
+
+def random_phase_pilots(nt, P, power, seed=3):
+    return np.sqrt(power) * np.exp(2j * np.pi * np.random.RandomState(seed).rand(nt, P))
+
+
+def _envelope_case(nr, nt, P, pilots, rho_L, cov, noise_power):
+    """pilots: None (drawn), 'dft' or 'phases'; rho_L: the rho of L = chol(toeplitz_cov(nr, rho)), or None; cov: None, 'eye'
+    (0.49 I) or the rho of 0.49 toeplitz_cov(nr, rho)"""
+    s = None if pilots is None else (dft_pilots if pilots == "dft" else random_phase_pilots)(nt, P, 1.5)
+    L = None if rho_L is None else np.linalg.cholesky(toeplitz_cov(nr, rho_L))
+    C = None if cov is None else 0.49 * (np.eye(nr) if cov == "eye" else toeplitz_cov(nr, cov))
+    return default_cfg(nr=nr, nt=nt, n_pilots=P, pilot_power=1.5, noise_power=noise_power, alpha=0.7, pilots=s, L=L, cov=C)
+
+
+ENVELOPE_CASES = {
+    "a": _envelope_case(1, 1, 1, None, None, "eye", 2.0),         # smallest shape, 15 padded rows
+    "b": _envelope_case(15, 1, 2, None, 0.9, 0.9, 0.5),           # one padded row
+    "c": _envelope_case(17, 1, 9, "phases", 0.9, 0.9, 0.5),       # second row tile nearly empty, odd P
+    "d": _envelope_case(32, 1, 255, None, None, "eye", 16.0),     # largest odd P; complex128 above the default LDS limit
+    "e": _envelope_case(113, 1, 16, None, 0.7, 0.7, 1.0),         # first nr whose complex128 LDS passes 63 KiB
+    "f": _envelope_case(128, 1, 256, None, 0.7, 0.7, 16.0),       # the nt = 1 maximum: above the limit in both arithmetics
+    "g": _envelope_case(128, 8, 256, None, 0.7, None, 16.0),      # the overall LDS maximum; L with nt = 8
+    "h": _envelope_case(5, 4, 4, "dft", 0.9, None, 0.5),          # NTP = 4 unpadded, P = nt, L with nt > 1
+    "i": _envelope_case(33, 5, 12, None, 0.9, None, 0.5),         # NTP = 8 with 3 padded columns, L
+    "j": _envelope_case(16, 6, 7, "phases", None, None, 0.5),     # fixed pilots with nt > 1, nr = nrp
+    "k": _envelope_case(64, 7, 64, None, 0.7, None, 4.0),         # NTP = 8 with 1 padded column, L, four row tiles
+    "l": _envelope_case(3, 2, 3, "phases", 0.9, None, 0.5),       # 8 realizations per wavefront, L
+}
+LDS_BUDGET = 160 * 1024
+LDS_ATTRIBUTE_ABOVE = 63 * 1024         # a launch above this raises the kernel's dynamic-LDS limit first
+MAX_NR, MAX_NT, MAX_PIPELINE_PILOTS = 128, 8, 256
+
+
+def ntp_of(nt):
+    """nt rounded up to a power of two: the kernel instance, 16 / ntp realizations per wavefront"""
+    ntp = 1
+    while ntp < nt:
+        ntp *= 2
+    return ntp
+
+
+def pilot_mse_lds(nr, nt, P, random_pilots, real_bytes):
+    """Restatement of the launcher's LDS size per wavefront: the inverse Gram matrices (complex f64), four [nrp][16] real
+    planes, the pilots"""
+    nrp = (nr + 15) // 16 * 16
+    ng = 16 // ntp_of(nt) if random_pilots else 1
+    return ng * nt * nt * 16 + 4 * nrp * 16 * real_bytes + ng * nt * P * 2 * real_bytes
+
+
+def envelope_lds(cfg, dtype):
+    return pilot_mse_lds(cfg["nr"], cfg["nt"], cfg["n_pilots"], cfg["pilots"] is None, 8 if dtype == "f64" else 4)
+
+
+def envelope_kernel_name(cfg, dtype):
+    return "pilot_mse %s b%d %s%s" % (dtype, 16 // ntp_of(cfg["nt"]), "ls+mmse" if cfg["cov"] is not None else "ls",
+                                      " gl" if cfg["L"] is not None else "")
+
+
+def pilot_mse_per_trip(cfg, dtype, n_cu):
+    """Realizations one pass of the pipeline's grid takes with grid_oversub = 1: min(8, 160 KiB / LDS) one-wavefront
+    workgroups per compute unit, 16 / ntp realizations each"""
+    per_cu = max(1, min(8, LDS_BUDGET // envelope_lds(cfg, dtype)))
+    return n_cu * per_cu * (16 // ntp_of(cfg["nt"]))
