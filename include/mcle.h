@@ -738,6 +738,52 @@ typedef struct mcle_bd_cfg {            /* apps/comp_BD/simulate_comp_simple.py:
 int mcle_run_bd(mcle_ctx* ctx, int dtype, const mcle_bd_cfg* cfg, uint64_t seed, uint64_t first,
                 uint64_t count, mcle_counters* d_counters, uint32_t* d_sym_err, uint32_t* d_bit_err);
 
+/* ---- CoMP with an external interferer and per-realization stream reduction, fused (apps/comp_BD/simulate_comp.py:311-621,
+ *      simulate_comp_with_ext_int_simple.py): per realization draw big_H [K r][K r + n_ext], apply the path loss (block
+ *      (rx k, tx l) times sqrt(pathloss[k*K + l]), interferer column e of user k times sqrt(pathloss_ext[k*n_ext + e])),
+ *      solve WhiteningBD or EnhancedBD (the arithmetic of mcle_bd_extint, f64 for either dtype), for 'capacity' /
+ *      'effective_throughput' choose every user's stream count on the device (first maximum, as np.argmax), send n_symbols
+ *      per kept stream, add the interferers' data (power pe) and noise, filter, demodulate, count.
+ *      'effective_throughput' value of a candidate with post-filter SINRs s_i: sum_i Kb (1 - PER_i), PER = 1 - (1 - BER)^
+ *      packet_length, BER the closed form of the context's constellation (MCLE_CONST_BPSK, MCLE_CONST_QAM; any other kind is
+ *      taken as M-PSK), Q(x) = erfc(x / sqrt 2) / 2.
+ *      The app's six variants: None / 'naive' / 'fixed' / 'capacity' / 'effec_throughput' = method 1 with metric 0..4,
+ *      'Whitening' = method 0 (metric ignored).
+ * Draws (mcle-philox-v1, realization index = subsequence; n = K r):
+ *   stream 2 (channel)     user block entry (i, c) at i n + c -- the positions of mcle_run_bd; interferer entry (i, e) at
+ *                          n^2 + i n_ext + e
+ *   stream 0 (data)        active streams numbered q = 0, 1, .. in user order; symbol j of stream q at q n_symbols + j -- every
+ *                          variant sends the same data on its first streams (the app re-seeds its data generator per metric)
+ *   stream 1 (noise)       receive antenna i, symbol j at i n_symbols + j -- as mcle_run_bd
+ *   stream 3 (interferer)  CN(0, 1) sample e n_symbols + j, scaled by sqrt(pe)
+ *   Hence n_ext = 0 (or pe = 0), method 1, metric 0 gives the per-realization counts of mcle_run_bd(waterfilling = 0), and one
+ *   seed gives all variants common random numbers (the app draws fresh noise per metric; the statistics are the same).
+ * d_pathloss: NULL (the config's static set, has_pathloss = 0: all ones) or [count][K][K + n_ext], one set per realization
+ *   (rx user; tx users, then interferer antennas).
+ * Outputs, each NULL or: d_sym_err / d_bit_err [count] (0xFFFFFFFF: numerically singular channel, not counted);
+ *   d_stream_sym_err / d_stream_bit_err [count][K r] by stream slot k r + j (0 on an inactive stream); d_ns [count][K];
+ *   d_sinr [count][K r], linear, 0 on an inactive stream: MultiUserChannelMatrixExtInt.calc_JP_SINR with interferer power
+ *   sinr_pe -- the app calls it WITHOUT pe, so its sinr_* results use 1.0 (simulate_comp.py:592); pass sinr_pe = 1 to
+ *   reproduce that.  d_counters: n_symbols / n_bits are the figures with every stream active (K r n_symbols per realization);
+ *   a realization sent n_symbols * sum_k d_ns[.][k].
+ * Envelope: 1 <= K <= 4, 1 <= r <= 4, K r <= 8, 0 <= n_ext <= 8, n_symbols >= 1, M <= 256.  count = 0 returns MCLE_OK and
+ * launches nothing.  The per-realization arrays do not depend on the grid or on how [first, first + count) is split.
+ * mcle_ctx_last_kernel: "comp_link f64|f32 r<r> pairs|single" (pairs: n_symbols even, two columns per lane). */
+typedef struct mcle_comp_cfg {
+    int32_t K, r, n_ext, n_symbols, demod_method;
+    int32_t method;          /* 0 WhiteningBD, 1 EnhancedBD */
+    int32_t metric;          /* 0 None, 1 naive, 2 fixed, 3 capacity, 4 effective_throughput */
+    int32_t num_streams;     /* naive / fixed */
+    int32_t packet_length;   /* effective_throughput */
+    int32_t has_pathloss;
+    double iPu, noise_var, pe, sinr_pe;
+    double pathloss[16], pathloss_ext[32];
+} mcle_comp_cfg;
+int mcle_run_comp(mcle_ctx* ctx, int dtype, const mcle_comp_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
+                  const double* d_pathloss /* NULL or [count][K][K + n_ext], one set per realization */,
+                  mcle_counters* d_counters, uint32_t* d_sym_err, uint32_t* d_bit_err,
+                  uint32_t* d_stream_sym_err, uint32_t* d_stream_bit_err, int32_t* d_ns, double* d_sinr);
+
 /* ---- pilot-based channel estimation from CAZAC reference signals (reference_signals/channel_estimation.py:73-131
  *      CazacBasedChannelEstimator, :135-251 CazacBasedWithOCCChannelEstimator) ----------------------------------
  * out = FFT_{m ne}( IFFT_{ne}(conj(ref) * y)[0 : num_taps_to_keep + 1] ), times ne when `normalized` (a sequence of unit

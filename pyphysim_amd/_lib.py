@@ -103,6 +103,18 @@ class BdExtIntCfg(Structure):
                 ("noise_var", c_double), ("pe", c_double)]
 
 
+class CompCfg(Structure):
+    _fields_ = [("K", c_int32), ("r", c_int32), ("n_ext", c_int32), ("n_symbols", c_int32), ("demod_method", c_int32),
+                ("method", c_int32), ("metric", c_int32), ("num_streams", c_int32), ("packet_length", c_int32),
+                ("has_pathloss", c_int32), ("iPu", c_double), ("noise_var", c_double), ("pe", c_double),
+                ("sinr_pe", c_double), ("pathloss", c_double * 16), ("pathloss_ext", c_double * 32)]
+
+
+# mcle_run_comp: the variants of apps/comp_BD/simulate_comp.py -> (method, metric)
+COMP_VARIANTS = {"None": (1, 0), None: (1, 0), "naive": (1, 1), "fixed": (1, 2), "capacity": (1, 3),
+                 "effective_throughput": (1, 4), "effec_throughput": (1, 4), "Whitening": (0, 0), "whitening": (0, 0)}
+
+
 BD_METRICS = {None: 0, "None": 0, "naive": 1, "fixed": 2, "capacity": 3, "candidates": 4, "per_user": 5}
 
 
@@ -253,6 +265,7 @@ _PROTOS = {
     "mcle_block_diagonalize": (c_int, [_P, _P, c_int, c_int, c_double, c_double, c_int, _P, _P, _P, _P, _P, c_size_t]),
     "mcle_pinv": (c_int, [_P, _P, c_int, c_int, c_double, _P, c_size_t]),
     "mcle_run_bd": (c_int, [_P, c_int, POINTER(BdCfg), c_uint64, c_uint64, c_uint64, _P, _P, _P]),
+    "mcle_run_comp": (c_int, [_P, c_int, POINTER(CompCfg), c_uint64, c_uint64, c_uint64, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mcle_cazac_estimate": (c_int, [_P, c_int, _P, c_int, _P, c_size_t, c_int, POINTER(c_double), c_int, c_int, c_int, _P]),
     "mcle_run_chanest": (c_int, [_P, c_int, POINTER(ChanestCfg), c_uint64, c_uint64, c_uint64, _P, _P]),
     "mcle_cazac_cancel": (c_int, [_P, c_int, _P, c_int, _P, _P, c_size_t, c_int, _P]),

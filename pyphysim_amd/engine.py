@@ -1101,6 +1101,63 @@ class Engine:
                 cfg.pathloss[i] = float(v)
         return self._run(self.lib.mcle_run_bd, cfg, seed, first, count, dtype, per_realization, counters)
 
+    def run_comp(self, K, r, n_ext, n_symbols, iPu, noise_var, pe, seed, first, count, variant="None", num_streams=1,
+                 packet_length=60, pathloss=None, pathloss_ext=None, pathloss_per_realization=None, sinr_pe=1.0,
+                 method=DEMOD_MINDIST, dtype=None, per_realization=False, counters=None):
+        """apps/comp_BD/simulate_comp.py fused (csrc/pipeline_comp.hip, include/mcle.h at mcle_run_comp): K cells of r x r
+        antennas, n_ext interferer antennas of power pe, one of the app's variants 'None' / 'naive' / 'fixed' / 'capacity' /
+        'effec_throughput' / 'Whitening'; n_symbols per kept stream.  pathloss [K, K] (rx user, tx user) and pathloss_ext
+        [K, n_ext], or pathloss_per_realization [count, K, K + n_ext] (host or device array).
+        -> the counters dict; with per_realization=True (counters, dict(sym_err [count], bit_err [count],
+        stream_sym_err [count, K r], stream_bit_err [count, K r], ns [count, K], sinr [count, K r]))."""
+        if variant not in _lib.COMP_VARIANTS:
+            raise ValueError("unknown variant %r (known: None, naive, fixed, capacity, effec_throughput, Whitening)" % (variant,))
+        K, r, n_ext, count = int(K), int(r), int(n_ext), int(count)
+        cfg = _lib.CompCfg()
+        cfg.K, cfg.r, cfg.n_ext, cfg.n_symbols, cfg.demod_method = K, r, n_ext, int(n_symbols), int(method)
+        cfg.method, cfg.metric = _lib.COMP_VARIANTS[variant]
+        cfg.num_streams, cfg.packet_length = int(num_streams), int(packet_length)
+        cfg.iPu, cfg.noise_var, cfg.pe, cfg.sinr_pe = float(iPu), float(noise_var), float(pe), float(sinr_pe)
+        in_envelope = 1 <= K <= 4 and 0 <= n_ext <= 8           # anything else is refused by the library below
+        if (pathloss is None) != (pathloss_ext is None) and n_ext > 0:
+            raise ValueError("pathloss and pathloss_ext go together")
+        if pathloss is not None and in_envelope:
+            pl = np.asarray(pathloss, dtype=np.float64)
+            ple = np.zeros((K, 0)) if pathloss_ext is None else np.asarray(pathloss_ext, dtype=np.float64)
+            if pl.shape != (K, K) or ple.shape != (K, n_ext):
+                raise ValueError("pathloss must be [K, K] (rx user, tx user) and pathloss_ext [K, n_ext]")
+            cfg.has_pathloss = 1
+            for i, v in enumerate(pl.reshape(-1)):
+                cfg.pathloss[i] = float(v)
+            for i, v in enumerate(ple.reshape(-1)):
+                cfg.pathloss_ext[i] = float(v)
+        d_pl = None
+        if pathloss_per_realization is not None and in_envelope:
+            d_pl = pathloss_per_realization
+            if not isinstance(d_pl, DeviceArray):
+                d_pl = self.to_device(np.ascontiguousarray(d_pl, dtype=np.float64))
+            if tuple(d_pl.shape) != (count, K, K + n_ext) or d_pl.dtype != np.dtype(np.float64):
+                raise ValueError("pathloss_per_realization must be float64 [count, K, K + n_ext]")
+        dt = self._dt(dtype)
+        cnt = counters if counters is not None else self.zeros(1, np.dtype((np.void, ctypes.sizeof(Counters))))
+        out = {}
+        if per_realization:
+            n = K * r if in_envelope and 1 <= r <= 4 else 0
+            out = dict(sym_err=self.empty(count, np.uint32), bit_err=self.empty(count, np.uint32),
+                       stream_sym_err=self.empty((count, n), np.uint32), stream_bit_err=self.empty((count, n), np.uint32),
+                       ns=self.empty((count, K), np.int32), sinr=self.empty((count, n), np.float64))
+        ptr = lambda name: out[name].ptr if per_realization else None
+        self._raise_value(self.lib.mcle_run_comp(self.ctx, dt, byref(cfg), int(seed), int(first), count,
+                                                 d_pl.ptr if (d_pl is not None and count) else None, cnt.ptr, ptr("sym_err"),
+                                                 ptr("bit_err"), ptr("stream_sym_err"), ptr("stream_bit_err"), ptr("ns"),
+                                                 ptr("sinr")))
+        if counters is not None and not per_realization:
+            return None
+        res = None if counters is not None else self._counters(cnt)
+        if per_realization:
+            return res, {k: v.get() for k, v in out.items()}
+        return res
+
     # ---- pilot-based channel estimation (csrc/kernels_chanest.hip) ------------------------------------
     def cazac_estimate(self, ref_seq, rx, num_taps_to_keep, size_multiplier=2, normalized=False, cover=None, dtype=None):
         """CazacBasedChannelEstimator.estimate_channel_freq_domain on rows: ref_seq [ne]; rx [..., ne], or

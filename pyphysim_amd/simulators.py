@@ -522,3 +522,129 @@ class PilotEstimationSimulator(BatchedSimulationRunner):
             res.add_result(Result.from_batch("mse_mmse", Result.RATIOTYPE, e_mm, float(n), e_mm, float(c.get("err_mmse_sq", 0.0)), n))
         res.add_result(Result.from_batch("channel_power", Result.RATIOTYPE, pw, float(n), pw, float(c.get("pow_sq", 0.0)), n))
         return res
+
+
+class CompSimulator(BatchedSimulationRunner):
+    """CoMP with an external interferer and stream reduction (the reference's apps/comp_BD/simulate_comp.py and its script
+    form simulate_comp_with_ext_int_simple.py): `K` cells of `Nr` x `Nr` antennas precode jointly by block diagonalisation
+    while an interferer of rank `ext_int_rank` and power `Pe_dBm` disturbs every user; each of the `variants` ('None',
+    'naive', 'fixed', 'capacity', 'effec_throughput': EnhancedBD with that metric; 'Whitening': WhiteningBD) is run on the
+    same realizations -- one Engine.run_comp per variant and batch on the same seed, so the variants share channel, data,
+    interferer and noise draws (the app draws fresh noise per metric; the statistics are the same).  'SNR' and 'Pe_dBm' are
+    unpacked.  The transmit power follows the app's rule (pathloss.transmit_power_for_border_loss): SNR at the cell border,
+    whose loss is `path_loss_border` (default: PathLoss3GPP1 at 1 km when a path loss is given, else 1).
+
+    `pathloss` [K, K] (rx user, tx cell) and `pathloss_ext` [K, ext_int_rank]: arrays, or `pathloss` a callable
+    (first, count) -> [count, K, K + ext_int_rank] for per-drop scenarios (cell geometry itself is out of scope).
+
+    Results per variant v, formed per realization and per stream as simulate_comp.py:556-621 does: 'ber_v', 'ser_v',
+    'per_v' (per = 1 - (1 - ber_stream)^packet_length, errors = per x packages, summed over the streams), 'spec_effic_v'
+    (sum (1 - per) Kb, RATIO against 1), 'sinr_v' (calc_JP_SINR with unit interferer power -- the app's call -- one update
+    per stream).  Sums and sums of squares travel through EXTRA_KEYS, so sharding and resume keep them."""
+
+    VARIANTS = ("None", "naive", "fixed", "capacity", "effec_throughput", "Whitening")
+    _RATIOS = ("ber", "ser", "per", "spec_effic")
+
+    def __init__(self, SNR, Pe_dBm, modulator="psk", M=4, K=3, Nr=2, ext_int_rank=1, NSymbs=500, packet_length=60,
+                 N0_dBm=-116.4, variants=VARIANTS, num_streams=1, pathloss=None, pathloss_ext=None, path_loss_border=None,
+                 rep_max=1000, seed=0, batch_size=4096, dtype="f64", demod="auto", engine=None,
+                 common_random_numbers=False, process_group=None):
+        super().__init__(batch_size=batch_size, process_group=process_group)
+        from .pathloss import PathLoss3GPP1
+        self.rep_max = rep_max
+        self.seed = int(seed)
+        self.dtype = dtype
+        self.common_random_numbers = common_random_numbers
+        self._engine = engine
+        self.modulator = make_modulator(modulator, M, engine) if isinstance(modulator, str) else modulator
+        if demod == "auto":
+            demod = "slicer" if isinstance(self.modulator, QAM) else "mindist"
+        self.demod_method = _lib.DEMOD_QAM_SLICER if demod == "slicer" else _lib.DEMOD_MINDIST
+        self.variants = tuple(variants)
+        for v in self.variants:
+            if v not in self.VARIANTS:
+                raise ValueError("unknown variant %r (known: %s)" % (v, ", ".join(self.VARIANTS)))
+        self._pl_call = pathloss if callable(pathloss) else None
+        self._pl = self._ple = None
+        if pathloss is not None and self._pl_call is None:
+            self._pl = np.asarray(pathloss, dtype=float)
+            self._ple = np.zeros((int(K), 0)) if pathloss_ext is None else np.asarray(pathloss_ext, dtype=float)
+            if self._pl.shape != (int(K), int(K)) or self._ple.shape != (int(K), int(ext_int_rank)):
+                raise ValueError("pathloss must be [K, K] and pathloss_ext [K, ext_int_rank]")
+        if path_loss_border is None:
+            path_loss_border = 1.0 if pathloss is None else PathLoss3GPP1().calc_path_loss(1.0)
+        self.path_loss_border = float(path_loss_border)
+        keys = []
+        for v in self.variants:
+            keys += ["%s_%s_%s" % (m, v, s) for m in self._RATIOS for s in ("value", "total", "sum", "sq")]
+            keys += ["sinr_%s_sum" % v, "sinr_%s_sq" % v, "sinr_%s_n" % v, "n_%s" % v]
+        self.EXTRA_KEYS = tuple(keys)
+        self.params.add("SNR", np.atleast_1d(np.asarray(SNR, dtype=float)))
+        self.params.add("Pe_dBm", np.atleast_1d(np.asarray(Pe_dBm, dtype=float)))
+        self.params.set_unpack_parameter("SNR")
+        self.params.set_unpack_parameter("Pe_dBm")
+        for k, v in (("modulator", self.modulator.name), ("K", int(K)), ("Nr", int(Nr)), ("ext_int_rank", int(ext_int_rank)),
+                     ("NSymbs", int(NSymbs)), ("packet_length", int(packet_length)), ("N0_dBm", float(N0_dBm)),
+                     ("num_streams", int(num_streams))):
+            self.params.add(k, v)
+
+    engine = _LinkSimulator.engine
+    _seed_for = _LinkSimulator._seed_for
+    _bind = _LinkSimulator._bind
+
+    def _run_batch(self, current_parameters, first_rep, count):
+        from .pathloss import transmit_power_for_border_loss
+        p = current_parameters
+        eng = self._bind()
+        K, r, E, NS, L = p["K"], p["Nr"], p["ext_int_rank"], p["NSymbs"], p["packet_length"]
+        Kb = int(self.modulator.K)
+        noise_var = 10.0 ** (p["N0_dBm"] / 10.0) / 1000.0
+        pe = 10.0 ** (float(p["Pe_dBm"]) / 10.0) / 1000.0
+        iPu = transmit_power_for_border_loss(p["SNR"], p["N0_dBm"], self.path_loss_border)
+        per_drop = None
+        if self._pl_call is not None and count:
+            per_drop = eng.to_device(np.ascontiguousarray(self._pl_call(int(first_rep), int(count)), dtype=np.float64))
+        c = None
+        slot = np.arange(K * r) % r
+        for v in self.variants:
+            res, a = eng.run_comp(K, r, E, NS, iPu, noise_var, pe, self._seed_for(p), first_rep, count, variant=v,
+                                  num_streams=p["num_streams"], packet_length=L, pathloss=self._pl, pathloss_ext=self._ple,
+                                  pathloss_per_realization=per_drop, sinr_pe=1.0, method=self.demod_method,
+                                  dtype=self.dtype, per_realization=True)
+            if c is None:
+                c = dict(res)
+            ok = a["sym_err"] != 0xFFFFFFFF
+            active = (slot[None, :] < np.repeat(a["ns"], r, axis=1)) & ok[:, None]
+            n_act = active.sum(axis=1).astype(float)
+            sbit = np.where(active, a["stream_bit_err"], 0).astype(float)
+            ssym = np.where(active, a["stream_sym_err"], 0).astype(float)
+            num_bits = float(NS * Kb)
+            per_s = np.where(active, 1.0 - (1.0 - sbit / num_bits) ** L, 0.0)
+            packages = num_bits / L
+            pairs = dict(ber=(sbit.sum(axis=1), n_act * num_bits), ser=(ssym.sum(axis=1), n_act * float(NS)),
+                         per=((per_s * packages).sum(axis=1), n_act * packages),
+                         spec_effic=(np.where(active, (1.0 - per_s) * Kb, 0.0).sum(axis=1), np.ones(int(count))))
+            for m, (num, den) in pairs.items():
+                ratio = num[ok] / den[ok]
+                c["%s_%s_value" % (m, v)], c["%s_%s_total" % (m, v)] = float(num[ok].sum()), float(den[ok].sum())
+                c["%s_%s_sum" % (m, v)], c["%s_%s_sq" % (m, v)] = float(ratio.sum()), float(np.square(ratio).sum())
+            s = a["sinr"][active]
+            c["sinr_%s_sum" % v], c["sinr_%s_sq" % v] = float(s.sum()), float(np.square(s).sum())
+            c["sinr_%s_n" % v], c["n_%s" % v] = float(s.size), float(ok.sum())
+        if c is None:
+            c = {k: 0 for k in self.COUNTER_KEYS + ("n_symbols", "n_bits")}
+        return c
+
+    def _results_from_counters(self, current_parameters, c):
+        from .simulations import Result, SimulationResults
+        res = SimulationResults()
+        g = lambda k: float(c.get(k, 0.0))
+        for v in self.variants:
+            n = int(round(g("n_%s" % v)))
+            for m in self._RATIOS:
+                res.add_result(Result.from_batch("%s_%s" % (m, v), Result.RATIOTYPE, g("%s_%s_value" % (m, v)),
+                                                 g("%s_%s_total" % (m, v)), g("%s_%s_sum" % (m, v)), g("%s_%s_sq" % (m, v)), n))
+            ns = int(round(g("sinr_%s_n" % v)))
+            res.add_result(Result.from_batch("sinr_%s" % v, Result.RATIOTYPE, g("sinr_%s_sum" % v), float(ns),
+                                             g("sinr_%s_sum" % v), g("sinr_%s_sq" % v), ns))
+        return res

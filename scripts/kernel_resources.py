@@ -23,7 +23,7 @@ CSRC = os.path.join(REPO, "pyphysim_amd", "csrc")
 LLVM = "/opt/rocm/lib/llvm/bin"
 # kernels listed per translation unit (every *.o of the in-tree build is read: `make -C pyphysim_amd/csrc` first)
 PREFIXES = ("k_run_", "k_link_walk", "k_mimo_filters", "k_tdl_symbol_polys", "k_mimo_tdl_symbol_polys", "k_mimo_flat_", "k_ia_solve_links",
-            "k_ia_link", "k_bd_solve_links", "k_bd_link", "k_ofdm_mod_1024_mfma", "k_ofdm_demod_1024_mfma", "k_jakes_blocks",
+            "k_ia_link", "k_bd_solve_links", "k_bd_link", "k_comp_solve_links", "k_comp_link", "k_ofdm_mod_1024_mfma", "k_ofdm_demod_1024_mfma", "k_jakes_blocks",
             "k_jakes_mfma", "k_cazac_estimate", "k_cazac_cancel", "k_chanest", "k_ls_estimate", "k_mmse_estimate",
             "k_pilot_mse", "k_codebook")
 KEYS = (".vgpr_count", ".agpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count",
