@@ -949,6 +949,47 @@ int mcle_codebook_generate(mcle_ctx* ctx, int dtype, int type, int K, int Nt, in
 int mcle_run_codebook_search(mcle_ctx* ctx, int dtype, const mcle_codebook_cfg* cfg, uint64_t seed, uint64_t first,
                              uint64_t count, mcle_codebook_result* out, double* d_min_d2, int32_t* d_pair);
 
+/* ---- limited-feedback IA: codebook channel quantizer and fused link (apps/ia/simple_maxsinr_quantized.py) ------------------
+ * mcle_quantize_links: quant_small_matrix / my_quant_func (app :90-154) on a batch.  Every nr x nt block (receiver k1,
+ * transmitter k2) of d_bigH [batch][K nr][K nt] is flattened row-major to v and takes the nearest row c of d_codebook
+ * [n_codewords][dim = nr nt] (row = codeword, entry order = small_matrix.reshape(-1); complex of the call's dtype):
+ *     metric 0 (calc_dist, app :40-63):        d = || v / ||v|| - c ||^2, evaluated as 1 + ||c||^2 - 2 Re(c^H v^) so that injected
+ *                                              codewords need not have unit norm;
+ *     metric 1 (calc_angle_dist, app :66-87):  d = 1 - |c^H v|^2 / (||v||^2 ||c||^2)   (codewords must be non-zero).
+ * The lowest index wins a tie (numpy.argmin).  A block whose entries are all zero takes codeword 0 and d = NaN (argmin over the
+ * reference's all-NaN distances).  d_index [batch][K][K] (int32); d_bigHq (may be NULL) [batch][K nr][K nt]: every block a bit copy
+ * of its codeword; d_dist (may be NULL) [batch][K][K]: the chosen distance (double in either arithmetic).
+ * Envelope: 1 <= K <= 4, 1 <= nr, nt <= 6, 1 <= n_codewords <= 4096, metric 0 / 1, batch K^2 <= 2^31-1; anything else is
+ * MCLE_E_INVAL with a message that names the argument (the shape rules are checked before the context and the pointers).
+ * batch = 0 returns MCLE_OK and launches nothing.
+ * The search is a real matrix product (16 codewords x 16 links per tile, inner dimension [Re; Im] of the dim entries) on
+ * v_mfma_f64_16x16x4_f64 / v_mfma_f32_16x16x4_f32 followed by a column minimum taken in index order: no output depends on the grid,
+ * on MCLE_OPT_GRID_OVERSUB, on the position of a link in its strip of 16 or on how a batch is split, bit for bit.  Scaling d_bigH
+ * by a power of two changes nothing; multiplying a link by j changes nothing under metric 1.
+ * mcle_ctx_last_kernel: "quantize_links f64|f32 m<metric>".
+ *
+ * mcle_run_ia_quantized: mcle_run_ia (K = 3, 2 x 2, one stream; every solver; either arithmetic) with the solver seeing only the
+ * quantized channel: three launches per slice -- (1) draw big_H and quantize its 9 links (the search above), (2) redraw big_H,
+ * gather the nine 2 x 2 blocks from the codebook by index, run the solver on them and record G_kl = U_k H_kl F_l on the TRUE H,
+ * (3) the symbol walk of mcle_run_ia, untouched.  The draws are those of mcle_run_ia for the same (seed, realization): a perfect-CSI
+ * run and a quantized run of one seed are on common random numbers.  A singular quantized system is flagged skipped as today.
+ * d_sum_capacity: sum_k log2(1 + SINR_k), SINR_k = |G_kk|^2 / (sum_{l != k} |G_kl|^2 + noise_var ||U_k||^2) -- MultiUserChannelMatrix.
+ * calc_SINR on the true channel (app :272-273), not the solver's own figure.  d_index (may be NULL) [count][3][3]; d_dist_sum (may
+ * be NULL) [count]: the sum of the realization's nine chosen distances in link order.  qcfg: K = 3, nr = nt = 2. */
+enum { MCLE_QUANT_EUCLIDEAN = 0, MCLE_QUANT_CHORDAL = 1 };
+typedef struct mcle_quant_cfg {
+    int32_t K, nr, nt;                  /* 1 <= K <= 4, 1 <= nr, nt <= 6 : dim = nr*nt <= 36 */
+    int32_t n_codewords;                /* 1 .. 4096 */
+    int32_t metric;                     /* MCLE_QUANT_*: 0 calc_dist, 1 calc_angle_dist */
+    int32_t reserved[3];
+} mcle_quant_cfg;
+int mcle_quantize_links(mcle_ctx* ctx, int dtype, const mcle_quant_cfg* cfg, const void* d_bigH, const void* d_codebook,
+                        int32_t* d_index, void* d_bigHq, double* d_dist, size_t batch);
+int mcle_run_ia_quantized(mcle_ctx* ctx, int dtype, const mcle_ia_cfg* cfg, const mcle_quant_cfg* qcfg, const void* d_codebook,
+                          uint64_t seed, uint64_t first, uint64_t count, mcle_counters* d_counters, uint32_t* d_sym_err,
+                          uint32_t* d_bit_err, double* d_sum_capacity, uint32_t* d_iterations, int32_t* d_index,
+                          double* d_dist_sum);
+
 /* ---- same-seed parity mode: NumPy's legacy global RandomState replayed on the device -------
  * Realization r receives exactly what the reference draws after np.random.seed(seed_base + r)
  * (legacy MT19937; util/misc.py:327-355 randn_c = randn real block then imag block, and

@@ -165,6 +165,14 @@ class CodebookResult(Structure):
 CODEBOOK_TYPES = {"complex": 0, "real": 1, "qegt": 2}
 
 
+class QuantCfg(Structure):
+    _fields_ = [("K", c_int32), ("nr", c_int32), ("nt", c_int32), ("n_codewords", c_int32), ("metric", c_int32),
+                ("reserved", c_int32 * 3)]
+
+
+QUANT_METRICS = {"euclidean": 0, "chordal": 1}
+
+
 class LegacySeg(Structure):
     _fields_ = [("kind", c_int32), ("n", c_int32), ("range", c_uint32), ("reserved", c_uint32)]
 
@@ -277,6 +285,9 @@ _PROTOS = {
     "mcle_codebook_generate": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_uint64, c_uint64, c_uint64, _P]),
     "mcle_run_codebook_search": (c_int, [_P, c_int, POINTER(CodebookCfg), c_uint64, c_uint64, c_uint64, POINTER(CodebookResult),
                                          _P, _P]),
+    "mcle_quantize_links": (c_int, [_P, c_int, POINTER(QuantCfg), _P, _P, _P, _P, _P, c_size_t]),
+    "mcle_run_ia_quantized": (c_int, [_P, c_int, POINTER(IaCfg), POINTER(QuantCfg), _P, c_uint64, c_uint64, c_uint64, _P, _P, _P,
+                                      _P, _P, _P, _P]),
     "mcle_legacy_draws": (c_int, [_P, POINTER(LegacySeg), c_int, c_uint32, c_uint64, c_uint64, _P, c_size_t, _P,
                                   c_size_t, _P]),
     "mcle_complex_from_parts": (c_int, [_P, c_int, _P, _P, c_double, _P, c_size_t]),

@@ -17,6 +17,7 @@
 #include "qam_pack.hpp"
 #include "wave_draws.hpp"
 #include "walk_f64.hpp"
+#include "quant.hpp"
 
 namespace mcle {
 
@@ -503,20 +504,49 @@ constexpr int kIaRec = 16;      // G[9], U[6], {ok, 0}
 // ITER = false: the closed-form solver only (config 5).  One kernel for both used to carry the iterative solvers' call frames
 // (ia_iterative is __noinline__) into the closed-form launches too: 322 VGPRs + 66 AGPRs and 1 792 B of scratch per lane for a
 // solve that needs neither.
-template <typename T, bool ITER>
+//
+// QUANT = true (mcle_run_ia_quantized, limited feedback): the solver sees the nine 2 x 2 blocks gathered from the codebook by the
+// indices of the quantize launch (kernels_quant.hip); the record's G_kl = U_k H_kl F_l is taken on the TRUE (redrawn) H, and the
+// capacity is MultiUserChannelMatrix.calc_SINR on that G -- not the solver's own figure.  The QUANT = false instantiations carry
+// an empty argument block and compile to what they were.
+template <typename T, bool QUANT> struct IaQuantSrc {};
+template <typename T> struct IaQuantSrc<T, true> {
+    const cx<T>* codebook;      // [n_codewords][4]
+    const int32_t* index;       // [count][9]
+    const double* dist;         // [count][9] chosen distances
+    double* dist_sum;           // [count] (may be null)
+};
+
+template <typename T, bool ITER, bool QUANT = false>
 __global__ __launch_bounds__(64) void k_ia_solve_links(double noise_var, int solver, int init, int max_iter, double rel,
                                                        uint64_t seed, uint64_t first, uint64_t count,
                                                        cx<T>* __restrict__ recs, double* __restrict__ cap_out,
-                                                       uint32_t* __restrict__ iter_out) {
+                                                       uint32_t* __restrict__ iter_out, IaQuantSrc<T, QUANT> q) {
     const uint64_t rl = (uint64_t)blockIdx.x * 64 + threadIdx.x;
     if (rl >= count) return;
     const Rng rng(seed, first + rl);
     cd bigH[36];
-#pragma unroll
-    for (int i = 0; i < 18; ++i)            // big_H row-major, two CN samples per Philox block
-        cn_pair<double>(rng, STREAM_CHAN, (uint32_t)i, 1.0, bigH[2 * i], bigH[2 * i + 1]);
     M2 H[3][3];
-    load_blocks(bigH, H);
+    if constexpr (!QUANT) {
+#pragma unroll
+        for (int i = 0; i < 18; ++i)            // big_H row-major, two CN samples per Philox block
+            cn_pair<double>(rng, STREAM_CHAN, (uint32_t)i, 1.0, bigH[2 * i], bigH[2 * i + 1]);
+        load_blocks(bigH, H);
+    } else {
+        // the solver's H: the links' codewords; the true channel is drawn AFTER the solve, so the two never share the registers
+        double dsum = 0.0;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            const cx<T>* c = q.codebook + (size_t)q.index[rl * 9 + i] * 4;
+            M2& m = H[i / 3][i % 3];
+            m.a = mk<double>((double)c[0].x, (double)c[0].y);
+            m.b = mk<double>((double)c[1].x, (double)c[1].y);
+            m.c = mk<double>((double)c[2].x, (double)c[2].y);
+            m.d = mk<double>((double)c[3].x, (double)c[3].y);
+            dsum += q.dist[rl * 9 + i];
+        }
+        if (q.dist_sum) q.dist_sum[rl] = dsum;
+    }
     IaSolution s;
     int runned = 0;
     if (!ITER || solver == IA_CLOSED_FORM) {
@@ -532,19 +562,32 @@ __global__ __launch_bounds__(64) void k_ia_solve_links(double noise_var, int sol
         }
         s = ia_iterative(H, solver, noise_var, max_iter, rel, init, F0, runned);
     }
+    if constexpr (QUANT) {
+#pragma unroll
+        for (int i = 0; i < 18; ++i) cn_pair<double>(rng, STREAM_CHAN, (uint32_t)i, 1.0, bigH[2 * i], bigH[2 * i + 1]);
+        load_blocks(bigH, H);                   // from here on H is the true channel
+    }
     cx<T>* rec = recs + rl * kIaRec;
+    [[maybe_unused]] double cap_true = 0.0;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
+        [[maybe_unused]] double want = 0.0, den = QUANT ? noise_var * (cabs2(s.U[k].x) + cabs2(s.U[k].y)) : 0.0;
 #pragma unroll
         for (int l = 0; l < 3; ++l) {
             const V2 hf = mvec(H[k][l], s.F[l]);
             const cd g = cadd(cmul(s.U[k].x, hf.x), cmul(s.U[k].y, hf.y));
             rec[3 * k + l] = mk<T>((T)g.x, (T)g.y);
+            if constexpr (QUANT) {
+                if (l == k) want = cabs2(g);
+                else den += cabs2(g);
+            }
         }
         rec[9 + 2 * k] = mk<T>((T)s.U[k].x.x, (T)s.U[k].x.y);
         rec[9 + 2 * k + 1] = mk<T>((T)s.U[k].y.x, (T)s.U[k].y.y);
+        if constexpr (QUANT) cap_true += log2(1.0 + want / den);
     }
     rec[15] = mk<T>(s.ok ? (T)1 : (T)0, (T)0);
+    if constexpr (QUANT) s.capacity = cap_true;
     if (cap_out) cap_out[rl] = s.capacity;
     if (iter_out) iter_out[rl] = (uint32_t)runned;
 }
@@ -708,22 +751,50 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? MCLE_F32_WALK_WAVES : 3) void
 
 constexpr uint64_t kSolveSlice = 1ull << 20;   // realizations per solve + walk pair: bounds the record buffer (128 MB here)
 
+// the limited-feedback run (mcle_run_ia_quantized); null: perfect CSI
+struct IaQuantRun {
+    const mcle_quant_cfg* qcfg;
+    const void* d_codebook;
+    int32_t* d_index;       // [count][9] (may be null)
+    double* d_dist_sum;     // [count] (may be null)
+};
+
 template <typename T>
 int run_ia_impl(mcle_ctx* ctx, const mcle_ia_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
-                mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit, double* d_cap, uint32_t* d_iter) {
+                mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit, double* d_cap, uint32_t* d_iter,
+                const IaQuantRun* qr = nullptr) {
     int rc;
     void* recs = nullptr;
     const uint64_t slice = count < kSolveSlice ? count : kSolveSlice;
-    if ((rc = ctx->scratch((size_t)slice * kIaRec * sizeof(cx<T>), &recs))) return rc;
+    // quantized: the slice's chosen distances [slice][9] (double) and indices [slice][9] (int32) follow the records
+    const size_t rec_bytes = (size_t)slice * kIaRec * sizeof(cx<T>);
+    if ((rc = ctx->scratch(rec_bytes + (qr ? (size_t)slice * 9 * (sizeof(double) + sizeof(int32_t)) : 0), &recs))) return rc;
+    double* q_dist = reinterpret_cast<double*>(static_cast<char*>(recs) + rec_bytes);
+    int32_t* q_index = reinterpret_cast<int32_t*>(q_dist + slice * 9);
     const ModemParams<T> mp = pipe_modem<T>(ctx, cfg->demod_method);
     const size_t lds = (size_t)mp.grid.G * mp.grid.G * sizeof(unsigned long long);
     const int per_wave = 16;      // 4 ... 64 realizations per wavefront measured: 1.98-2.05e8 realizations/s, no trend
     for (uint64_t off = 0; off < count; off += slice) {
         const uint64_t n = count - off < slice ? count - off : slice;
-        auto solve = cfg->solver == IA_CLOSED_FORM ? k_ia_solve_links<T, false> : k_ia_solve_links<T, true>;
-        hipLaunchKernelGGL(solve, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, cfg->noise_var,
-                           cfg->solver, cfg->initialize_with, cfg->max_iterations, cfg->relative_factor, seed, first + off, n,
-                           (cx<T>*)recs, d_cap ? d_cap + off : nullptr, d_iter ? d_iter + off : nullptr);
+        if (qr) {
+            int32_t* idx = qr->d_index ? qr->d_index + off * 9 : q_index;
+            if ((rc = launch_quantize_drawn(ctx, sizeof(T) == 8 ? MCLE_F64 : MCLE_F32, qr->qcfg, qr->d_codebook, seed, first + off, n,
+                                            idx, q_dist)))
+                return rc;
+            IaQuantSrc<T, true> q;
+            q.codebook = (const cx<T>*)qr->d_codebook, q.index = idx, q.dist = q_dist;
+            q.dist_sum = qr->d_dist_sum ? qr->d_dist_sum + off : nullptr;
+            auto solve = cfg->solver == IA_CLOSED_FORM ? k_ia_solve_links<T, false, true> : k_ia_solve_links<T, true, true>;
+            hipLaunchKernelGGL(solve, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, cfg->noise_var,
+                               cfg->solver, cfg->initialize_with, cfg->max_iterations, cfg->relative_factor, seed, first + off, n,
+                               (cx<T>*)recs, d_cap ? d_cap + off : nullptr, d_iter ? d_iter + off : nullptr, q);
+        } else {
+            auto solve = cfg->solver == IA_CLOSED_FORM ? k_ia_solve_links<T, false> : k_ia_solve_links<T, true>;
+            hipLaunchKernelGGL(solve, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, cfg->noise_var,
+                               cfg->solver, cfg->initialize_with, cfg->max_iterations, cfg->relative_factor, seed, first + off, n,
+                               (cx<T>*)recs, d_cap ? d_cap + off : nullptr, d_iter ? d_iter + off : nullptr,
+                               IaQuantSrc<T, false>{});
+        }
         MCLE_LAUNCH_CHECK();
         const uint64_t chunks = (n + per_wave - 1) / per_wave;
         const uint64_t cap = (uint64_t)ctx->n_cu * (sizeof(T) == 4 ? 4 : 3);                    // workgroups of four wavefronts
@@ -757,6 +828,8 @@ int run_ia_impl(mcle_ctx* ctx, const mcle_ia_cfg* cfg, uint64_t seed, uint64_t f
 }  // namespace mcle
 
 using namespace mcle;
+
+static int check_run_ia(mcle_ctx* ctx, int dtype, const mcle_ia_cfg* cfg, uint64_t count);
 
 extern "C" {
 
@@ -798,9 +871,41 @@ int mcle_ia_iterative(mcle_ctx* ctx, int solver, int initialize_with, const void
     return MCLE_OK;
 }
 
+int mcle_run_ia_quantized(mcle_ctx* ctx, int dtype, const mcle_ia_cfg* cfg, const mcle_quant_cfg* qcfg, const void* d_codebook,
+                          uint64_t seed, uint64_t first, uint64_t count, mcle_counters* d_counters, uint32_t* d_sym_err,
+                          uint32_t* d_bit_err, double* d_sum_capacity, uint32_t* d_iterations, int32_t* d_index,
+                          double* d_dist_sum) {
+    int rc = check_run_ia(ctx, dtype, cfg, count);
+    if (rc) return rc;
+    if ((rc = quant_check_cfg(dtype, qcfg))) return rc;
+    MCLE_REQUIRE(qcfg->K == 3 && qcfg->nr == 2 && qcfg->nt == 2, "fused quantized IA pipeline supports K = 3, Nr = Nt = 2 (codewords of dimension 4)");
+    if (count == 0) return MCLE_OK;
+    MCLE_REQUIRE(d_codebook != nullptr, "null d_codebook");
+    if ((rc = ctx->bind())) return rc;
+    const IaQuantRun qr{qcfg, d_codebook, d_index, d_dist_sum};
+    return dtype == MCLE_F32 ? run_ia_impl<float>(ctx, cfg, seed, first, count, d_counters, d_sym_err, d_bit_err,
+                                                  d_sum_capacity, d_iterations, &qr)
+                             : run_ia_impl<double>(ctx, cfg, seed, first, count, d_counters, d_sym_err, d_bit_err,
+                                                   d_sum_capacity, d_iterations, &qr);
+}
+
 int mcle_run_ia(mcle_ctx* ctx, int dtype, const mcle_ia_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
                 mcle_counters* d_counters, uint32_t* d_sym_err, uint32_t* d_bit_err, double* d_sum_capacity,
                 uint32_t* d_iterations) {
+    int rc = check_run_ia(ctx, dtype, cfg, count);
+    if (rc) return rc;
+    if (count == 0) return MCLE_OK;
+    if ((rc = ctx->bind())) return rc;
+    return dtype == MCLE_F32 ? run_ia_impl<float>(ctx, cfg, seed, first, count, d_counters, d_sym_err, d_bit_err,
+                                                  d_sum_capacity, d_iterations)
+                             : run_ia_impl<double>(ctx, cfg, seed, first, count, d_counters, d_sym_err, d_bit_err,
+                                                   d_sum_capacity, d_iterations);
+}
+
+}  // extern "C"
+
+// the argument rules mcle_run_ia and mcle_run_ia_quantized share
+static int check_run_ia(mcle_ctx* ctx, int dtype, const mcle_ia_cfg* cfg, uint64_t count) {
     int rc = check_pipe(ctx, dtype, cfg ? cfg->demod_method : 0, cfg);
     if (rc) return rc;
     // ClosedFormIASolver.solve asserts K == 3 (algorithms.py:210); this kernel is its 2x2, Ns = 1 case
@@ -817,12 +922,5 @@ int mcle_run_ia(mcle_ctx* ctx, int dtype, const mcle_ia_cfg* cfg, uint64_t seed,
     MCLE_REQUIRE(!(cfg->solver == MCLE_IA_ALT_MIN && cfg->initialize_with == MCLE_IA_INIT_ALT_MIN),
                  "Can't use 'alt_min' initialization with 'AlternatingMinIASolver' class 'alt_min'");
     MCLE_REQUIRE(count <= 0x7fffffffull, "at most 2^31-1 realizations per call");
-    if (count == 0) return MCLE_OK;
-    if ((rc = ctx->bind())) return rc;
-    return dtype == MCLE_F32 ? run_ia_impl<float>(ctx, cfg, seed, first, count, d_counters, d_sym_err, d_bit_err,
-                                                  d_sum_capacity, d_iterations)
-                             : run_ia_impl<double>(ctx, cfg, seed, first, count, d_counters, d_sym_err, d_bit_err,
-                                                   d_sum_capacity, d_iterations);
+    return MCLE_OK;
 }
-
-}  // extern "C"

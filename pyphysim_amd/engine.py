@@ -923,6 +923,73 @@ class Engine:
             return res, sev, be.get(), caps, iters
         return res
 
+    def run_ia_quantized(self, n_symbols, noise_var, seed, first, count, codebook, metric="euclidean", method=DEMOD_MINDIST,
+                         dtype=None, per_realization=False, solver="max_sinr", max_iterations=120, relative_factor=1e-6,
+                         initialize_with="random"):
+        """Limited-feedback config 5 (mcle_run_ia_quantized; apps/ia/simple_maxsinr_quantized.py): run_ia with the solver
+        seeing only the channel quantized link by link to `codebook` [C, 4] (host array or DeviceArray of the call's dtype);
+        data, noise, BER and 'sum_capacity' are on the true channel, on the draws of run_ia for the same seed.  Returns what
+        run_ia returns plus 'quant_dist' (+ '_sq'): the realizations' sums of their nine chosen distances, summed over the
+        valid realizations; with per_realization=True also (sym_err, bit_err, capacities, iterations, index [count, 3, 3],
+        dist_sum [count])."""
+        dt = self._dt(dtype)
+        d_cb, _ = self._cin(codebook, dt)
+        if len(d_cb.shape) != 2 or d_cb.shape[1] != 4:
+            raise ValueError("codebook must be [C, 4] (got %s)" % (d_cb.shape,))
+        cfg = IaCfg(3, 2, 2, 1, int(n_symbols), int(method), float(noise_var), _lib.IA_SOLVERS[solver],
+                    int(max_iterations), float(relative_factor), _lib.IA_INITS[initialize_with], 0)
+        qcfg = _lib.QuantCfg(3, 2, 2, int(d_cb.shape[0]), int(_lib.QUANT_METRICS.get(metric, metric)))
+        cnt = self.new_counters()
+        se, be = self.empty(count, np.uint32), self.empty(count, np.uint32)
+        cap, its = self.empty(count, np.float64), self.empty(count, np.uint32)
+        dsum = self.empty(count, np.float64)
+        idx = self.empty((count, 3, 3), np.int32) if per_realization else None
+        self._raise_value(self.lib.mcle_run_ia_quantized(self.ctx, dt, byref(cfg), byref(qcfg), d_cb.ptr, int(seed), int(first),
+                                                         int(count), cnt.ptr, se.ptr, be.ptr, cap.ptr, its.ptr,
+                                                         idx.ptr if per_realization else None, dsum.ptr))
+        res = self._counters(cnt)
+        caps, dists, sev = cap.get(), dsum.get(), se.get()
+        iters = its.get().astype(np.int64)
+        valid = sev != 0xFFFFFFFF
+        res["sum_capacity"] = float(caps[valid].sum())
+        res["sum_capacity_sq"] = float(np.square(caps[valid]).sum())
+        iterative = solver != "closed_form"
+        res["ia_runned_iterations"] = int(iters[valid].sum()) if iterative else 0
+        res["ia_runned_iterations_sq"] = int(np.square(iters[valid]).sum()) if iterative else 0
+        res["quant_dist"] = float(dists[valid].sum())
+        res["quant_dist_sq"] = float(np.square(dists[valid]).sum())
+        if per_realization:
+            return res, sev, be.get(), caps, iters, idx.get(), dists
+        return res
+
+    def quantize_links(self, big_H, codebook, K, Nr, Nt, metric="euclidean", dtype=None, with_dist=False):
+        """my_quant_func (apps/ia/simple_maxsinr_quantized.py:113-154) on a batch (mcle_quantize_links): big_H [batch, K Nr, K Nt]
+        (or one [K Nr, K Nt]), codebook [C, Nr Nt] (row = codeword).  metric 'euclidean' = calc_dist, 'chordal' =
+        calc_angle_dist.  Returns (index [batch, K, K] int32, big_Hq like big_H[, dist [batch, K, K] float64]); device arrays in,
+        device big_Hq out."""
+        dt = self._dt(dtype)
+        d_H, host = self._cin(big_H, dt)
+        d_cb, _ = self._cin(codebook, dt)
+        K, Nr, Nt = int(K), int(Nr), int(Nt)
+        single = len(d_H.shape) == 2
+        if len(d_H.shape) not in (2, 3) or tuple(d_H.shape[-2:]) != (K * Nr, K * Nt):
+            raise ValueError("big_H must be [batch, K*Nr, K*Nt] (got %s)" % (d_H.shape,))
+        if len(d_cb.shape) != 2 or d_cb.shape[1] != Nr * Nt:
+            raise ValueError("codebook must be [C, Nr*Nt] (got %s)" % (d_cb.shape,))
+        b = 1 if single else int(d_H.shape[0])
+        qcfg = _lib.QuantCfg(K, Nr, Nt, int(d_cb.shape[0]), int(_lib.QUANT_METRICS.get(metric, metric)))
+        idx = self.empty((b, K, K), np.int32)
+        Hq = self.empty(d_H.shape, _lib.np_complex(dt))
+        dist = self.empty((b, K, K), np.float64) if with_dist else None
+        self._raise_value(self.lib.mcle_quantize_links(self.ctx, dt, byref(qcfg), d_H.ptr, d_cb.ptr, idx.ptr, Hq.ptr,
+                                                       dist.ptr if with_dist else None, b))
+        out = [idx.get(), self._out(Hq, host)] + ([dist.get()] if with_dist else [])
+        if single:
+            out[0] = out[0][0]
+            if with_dist:
+                out[2] = out[2][0]
+        return tuple(out)
+
     def ia_iterative(self, solver, big_H, F_init, noise_var, max_iterations=50, relative_factor=1e-6,
                      initialize_with="fix"):
         """IterativeIASolverBaseClass.solve (algorithms.py:802-883) with initialize_with='fix': big_H

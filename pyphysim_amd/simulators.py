@@ -345,6 +345,49 @@ class IaSimulator(_LinkSimulator):
         return res
 
 
+class QuantizedIaSimulator(IaSimulator):
+    """Limited-feedback IA: apps/ia/simple_maxsinr_quantized.py:170-273 as a simulator.  Every link of the 3-user 2x2
+    interference channel is fed back as the index of the nearest word of ``codebook`` [C, 4]; the solver (the app's
+    MaxSinrIASolver with 120 iterations by default) sees only the quantized channel, the precoded data cross the true one, and
+    'ber', 'ser' and 'sum_capacity' are those of the true channel.  Adds 'quant_dist' (RATIO: the sum of the chosen distances over
+    the links).  On the draws of IaSimulator for the same seed (common random numbers with the perfect-CSI run).
+
+    codebook: None draws ``codebook_size`` random unit-norm words (quantization.gen_codebook, seeded by ``seed``); a codebook
+    from CodebookFinder in G(4, 1), reshaped to [C, 4], is taken as is -- metric='chordal' is the one that matches it."""
+
+    def __init__(self, SNR, codebook=None, codebook_size=512, metric="euclidean", solver="max_sinr", max_iterations=120,
+                 modulator="bpsk", M=2, NSymbs=50, **kw):
+        super().__init__(SNR, modulator, M, NSymbs=NSymbs, solver=solver, max_iterations=max_iterations, **kw)
+        if metric not in _lib.QUANT_METRICS:
+            raise ValueError("metric must be 'euclidean' or 'chordal' (got %r)" % (metric,))
+        if codebook is None:
+            from .quantization import gen_codebook
+            codebook = gen_codebook(int(codebook_size), 4, seed=self.seed, engine=self.engine)
+        self.codebook = np.ascontiguousarray(np.asarray(codebook).reshape(-1, 4), dtype=np.complex128)
+        self.params.add("metric", metric)
+        self.params.add("codebook_size", int(self.codebook.shape[0]))
+
+    EXTRA_KEYS = IaSimulator.EXTRA_KEYS + ("quant_dist", "quant_dist_sq")
+
+    def _run_batch(self, current_parameters, first_rep, count):
+        eng = self._bind()
+        p = current_parameters
+        return eng.run_ia_quantized(p["NSymbs"], self._noise_var(p), self._seed_for(p), first_rep, count, self.codebook,
+                                    metric=p["metric"], method=self.demod_method, dtype=self.dtype, solver=p["solver"],
+                                    max_iterations=p["max_iterations"] if p["solver"] != "closed_form" else 1,
+                                    relative_factor=self.relative_factor,
+                                    initialize_with=p["initialize_with"] if p["solver"] != "closed_form" else "random")
+
+    def _results_from_counters(self, current_parameters, c):
+        from .simulations import Result
+        res = super()._results_from_counters(current_parameters, c)
+        n = max(int(c["n_realizations"]), 1)
+        d, d_sq = float(c.get("quant_dist", 0.0)), float(c.get("quant_dist_sq", 0.0))
+        # one update per realization: RATIO(sum of its nine distances, 9 links)
+        res.add_result(Result.from_batch("quant_dist", Result.RATIOTYPE, d, 9 * n, d / 9.0, d_sq / 81.0, n))
+        return res
+
+
 class ChannelEstimationSimulator(BatchedSimulationRunner):
     """Estimation-error Monte Carlo of the CAZAC-based channel estimator (the experiment of the reference's
     apps/simple_precoded_srs.py): `n_users` users send the SRS sequences of one root (cyclic shifts `shifts`) on the
