@@ -671,7 +671,7 @@ typedef struct mcle_bd_extint_cfg {
 int mcle_bd_extint(mcle_ctx* ctx, const mcle_bd_extint_cfg* cfg, const void* d_bigH, void* d_Ms, void* d_W,
                    int32_t* d_ns, double* d_cand_sinr, uint32_t* d_skipped, size_t batch);
 
-/* ---- iterative interference alignment for general geometries (SURVEY 8(f).3 tail): K <= 4 users with
+/* ---- iterative interference alignment for general geometries (SURVEY 8(f).3 tail): 2 <= K <= 4 users with
  *      Nr x Nt <= 6 x 6 antennas each (the reference's own application runs K = 3, Nr = 5, Nt = 3, Ns = 2,
  *      apps/ia/IA_Results_NrxNt(Ns).py:130-133) and per-user stream counts; AlternatingMinIASolver / MinLeakageIASolver /
  *      MaxSinrIASolver .solve (ia/algorithms.py:802-883, 885-1507) from injected precoders ('fix') or the 'svd'
@@ -686,7 +686,17 @@ int mcle_bd_extint(mcle_ctx* ctx, const mcle_bd_extint_cfg* cfg, const void* d_b
  *      d_skipped [batch] (a singular system met on the way), d_every_capacity [batch][256] (brute force only: the sum
  *      capacity of every stream combination in itertools.product order, last user fastest --
  *      BruteForceStreamIASolver.every_sum_capacity :2135-2145); every output but d_F / d_U may be NULL.
- *      Eigenvector phases are ours, not LAPACK's: SINRs, capacity and decisions do not depend on them. */
+ *      Eigenvector phases are ours, not LAPACK's: SINRs, capacity and decisions do not depend on them.
+ *      The envelope, refused with MCLE_E_INVAL before anything is launched: K in [2, 4]; Nr, Nt in [1, 6]; ns[k] in
+ *      [1, min(Nr, Nt)]; max_iterations >= 1; noise_var >= 0 (0 is allowed: a max-SINR matrix that loses its rank without
+ *      the noise term is solved as it is, and a realization whose result is not finite is flagged in d_skipped);
+ *      relative_factor >= 0; the 'svd' start and brute force (which starts from it) need Nr == Nt; brute force takes at
+ *      most 256 stream combinations (prod ns[k]).  min-leakage with more than one stream -- beyond the reference, whose
+ *      calc_Q_rev asserts -- scales its precoder (ns orthonormal eigenvectors) to unit Frobenius norm like the other two.
+ *      alt-min and min-leakage read each precoder from the right singular vectors of the stacked factor [X_k^H H_kl]_k
+ *      (one-sided Jacobi), not from the eigenvectors of the formed matrix: a leakage below eps |A|^2 keeps its digits.
+ *      d_skipped is set by a singular system in an update (max-SINR's B, alt-min's [H F, C]), in full_W_H, and by a sum
+ *      capacity that is not finite.  Sets mcle_ctx_last_kernel to "ia_general<D> K=.. NrxNt" (D = 4 or 6). */
 typedef struct mcle_ia_general_cfg {
     int32_t K, nr, nt;
     int32_t ns[4];

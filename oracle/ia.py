@@ -53,11 +53,12 @@ def full_W_H(H, F, W):
 
 
 def calc_SINR(H, F, U, noise_var):
-    """iabase.py:897-996 with P = 1 (full_F = F)."""
+    """iabase.py:897-996 with P = 1 (full_F = F); any number of users."""
+    K = len(F)
     sinr = []
-    for k in range(3):
+    for k in range(K):
         first = 0.0
-        for j in range(3):
+        for j in range(K):
             a = H[k][j] @ F[j]
             first = first + a @ a.conj().T
         s_k = np.empty(F[k].shape[1])
@@ -199,6 +200,8 @@ def min_leakage_solve(H, F_init, noise_var, max_iterations=50, relative_factor=1
         if W is None:
             W = update_W(F if full_F_first is None else full_F_first)
         F = [leig(_calc_Q_rev(H, W, k), Ns[k])[0] for k in range(K)]
+        # beyond the reference (one stream, where the eigenvector is the unit-norm precoder): unit power per user
+        F = [f / np.linalg.norm(f, "fro") if f.shape[1] > 1 else f for f in F]
         return F, update_W(F)
 
     F0 = [np.asarray(f, dtype=complex) for f in F_init]

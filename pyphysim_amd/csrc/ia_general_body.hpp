@@ -143,22 +143,6 @@ __device__ void heig(int n, Mat A, double* w, Mat& V) {
         }
     }
 }
-// eigenvectors of the m smallest eigenvalues, ascending (util/misc.py:210-255 leig)
-__device__ void leig(int n, const Mat& A, int m, Mat& out) {
-    double w[D];
-    Mat V;
-    heig(n, A, w, V);
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < m; ++j) out.a[i][j] = V.a[i][j];
-}
-// eigenvectors of the m largest eigenvalues, descending (util/misc.py:161-207 peig)
-__device__ void peig(int n, const Mat& A, int m, Mat& out) {
-    double w[D];
-    Mat V;
-    heig(n, A, w, V);
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < m; ++j) out.a[i][j] = V.a[i][n - 1 - j];
-}
 // A (n x n) X = B (n x m), Gaussian elimination with partial pivoting; X overwrites B
 __device__ bool solve(int n, Mat A, Mat& B, int m) {
     bool ok = true;
@@ -204,6 +188,91 @@ __device__ bool solve(int n, Mat A, Mat& B, int m) {
     return ok;
 }
 
+// Right singular vectors of a tall factor A (m x n, m <= (KM - 1) D rows: one block of at most D rows per other user) by
+// one-sided (Hestenes) complex Jacobi: the columns of A are rotated until they are orthogonal, V (n x n) collects the
+// rotations, w = squared singular values ascending, canonical phase per column like heig.  The eigenvectors of A^H A --
+// but the small singular values keep a RELATIVE accuracy that is lost once A^H A is formed: the leakage an aligned
+// precoder is read from is the square of a small singular value, and below eps |A|^2 the formed matrix holds only noise.
+struct Tall {
+    cd a[(KM - 1) * D][D];
+};
+__device__ void hsvd_right(int m, int n, Tall& A, double* w, Mat& V) {
+    mzero(V);
+    for (int i = 0; i < n; ++i) V.a[i][i] = mk<double>(1.0, 0.0);
+    double total = 0.0;
+    for (int k = 0; k < m; ++k)
+        for (int j = 0; j < n; ++j) total += abs2(A.a[k][j]);
+    for (int sweep = 0; sweep < 30; ++sweep) {
+        bool rotated = false;
+        for (int p = 0; p < n - 1; ++p)
+            for (int q = p + 1; q < n; ++q) {
+                double app = 0.0, aqq = 0.0;
+                cd apq = c0();                                // a_p^H a_q
+                for (int k = 0; k < m; ++k) {
+                    app += abs2(A.a[k][p]);
+                    aqq += abs2(A.a[k][q]);
+                    apq = cadd(apq, cmul(cconj(A.a[k][p]), A.a[k][q]));
+                }
+                const double g2 = abs2(apq);
+                // orthogonal to working accuracy, or a column that is rounding noise of the factor (its null space)
+                if (g2 <= 1e-32 * app * aqq || app <= 1e-30 * total || aqq <= 1e-30 * total) continue;
+                rotated = true;
+                const double g = sqrt(g2);
+                const cd e = cscale(apq, 1.0 / g);
+                const double tau = (aqq - app) / (2.0 * g);
+                const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
+                const double c = 1.0 / sqrt(1.0 + t * t), s = t * c;
+                for (int k = 0; k < m; ++k) {                 // A <- A J, the rotation of heig on the Gram entry
+                    const cd akp = A.a[k][p], akq = A.a[k][q];
+                    A.a[k][p] = csub(cscale(akp, c), cscale(cmul(akq, cconj(e)), s));
+                    A.a[k][q] = cadd(cscale(cmul(akp, e), s), cscale(akq, c));
+                }
+                for (int k = 0; k < n; ++k) {
+                    const cd vkp = V.a[k][p], vkq = V.a[k][q];
+                    V.a[k][p] = csub(cscale(vkp, c), cscale(cmul(vkq, cconj(e)), s));
+                    V.a[k][q] = cadd(cscale(cmul(vkp, e), s), cscale(vkq, c));
+                }
+            }
+        if (!rotated) break;
+    }
+    for (int j = 0; j < n; ++j) {
+        w[j] = 0.0;
+        for (int k = 0; k < m; ++k) w[j] += abs2(A.a[k][j]);
+    }
+    for (int i = 0; i < n - 1; ++i) {                         // ascending, carrying the columns of V
+        int mi = i;
+        for (int j = i + 1; j < n; ++j)
+            if (w[j] < w[mi]) mi = j;
+        if (mi != i) {
+            const double t = w[i];
+            w[i] = w[mi];
+            w[mi] = t;
+            for (int k = 0; k < n; ++k) {
+                const cd v = V.a[k][i];
+                V.a[k][i] = V.a[k][mi];
+                V.a[k][mi] = v;
+            }
+        }
+    }
+    for (int j = 0; j < n; ++j) {                             // canonical phase per column
+        int mi = 0;
+        double best = -1.0;
+        for (int k = 0; k < n; ++k) {
+            const double a = abs2(V.a[k][j]);
+            if (a > best * (1.0 + 1e-12)) {
+                best = a;
+                mi = k;
+            }
+        }
+        const double r = sqrt(best);
+        if (r > 0.0) {
+            const cd ph = cscale(cconj(V.a[mi][j]), 1.0 / r);
+            for (int k = 0; k < n; ++k) V.a[k][j] = cmul(V.a[k][j], ph);
+            V.a[mi][j].y = 0.0;
+        }
+    }
+}
+
 // ---- one realization ------------------------------------------------------------------------------------------
 struct Problem {
     const cd* bigH;     // [K nr][K nt], row-major
@@ -218,6 +287,7 @@ struct State {
     Mat F[KM];      // nt x ns[k]   (normalised precoders = full_F, P = 1)
     Mat W[KM];      // alt-min: C_k (nr x (nr - ns)); otherwise W_k (nr x ns)
     Mat WH[KM];     // ns x nr receive filters W^H after the solver finished
+    Mat X[KM];      // alt-min: the ns eigenvectors C_k leaves out (nr x ns), I - C_k C_k^H = X_k X_k^H
     int ns[KM];
 };
 
@@ -234,22 +304,10 @@ __device__ void calc_Q(const Problem& P, const State& S, const Mat* Fc, int k, b
     if (noise)
         for (int i = 0; i < P.nr; ++i) Q.a[i][i].x += P.nv;
 }
-// reverse network (iabase.py:642-667): sum_{l != k} (H_lk^H W_l)(H_lk^H W_l)^H, nt x nt
-__device__ void calc_Q_rev(const Problem& P, const State& S, int k, Mat& Q) {
-    mzero(Q);
-    Mat H, A;
-    for (int l = 0; l < P.K; ++l) {
-        if (l == k) continue;
-        P.block(l, k, H);
-        mm_h(H, S.W[l], P.nt, P.nr, S.ns[l], A);
-        add_outer(Q, A, P.nt, S.ns[l]);
-    }
-}
-
 // Fc: the precoders the covariances are built from (full_F of the reference: iabase.py:600-640, 828-894).  They are
 // S.F except in the first update of a greedy re-solve, where the wrapper has deleted a column from full_F without
 // renormalising it while F was renormalised (algorithms.py:1962-1975).
-__device__ void update_W(const Problem& P, State& S, int algo, const Mat* Fc) {
+__device__ void update_W(const Problem& P, State& S, int algo, const Mat* Fc, bool& ok) {
     Mat Q, H, A, Ac;
     for (int k = 0; k < P.K; ++k) {
         if (algo == 3) {     // max-SINR, per stream (algorithms.py:1376-1455)
@@ -270,56 +328,60 @@ __device__ void update_W(const Problem& P, State& S, int algo, const Mat* Fc) {
                     B.a[i][i].x += P.nv;
                     rhs.a[i][0] = A.a[i][l];
                 }
-                solve(P.nr, B, rhs, 1);
+                ok = solve(P.nr, B, rhs, 1) && ok;            // a singular B leaves a zero vector: 1 / sqrt(0) below
                 double nrm = 0.0;
                 for (int i = 0; i < P.nr; ++i) nrm += abs2(rhs.a[i][0]);
+                ok = ok && nrm > 0.0;
                 nrm = 1.0 / sqrt(nrm);
                 for (int i = 0; i < P.nr; ++i) S.W[k].a[i][l] = cscale(rhs.a[i][0], nrm);
             }
             scale(S.W[k], P.nr, S.ns[k], 1.0 / fro(S.W[k], P.nr, S.ns[k]));
         } else {
             calc_Q(P, S, Fc, k, true, Q);
-            if (algo == 1) peig(P.nr, Q, P.nr - S.ns[k], S.W[k]);    // alt-min: C_k, the interference subspace
-            else leig(P.nr, Q, S.ns[k], S.W[k]);                      // min leakage
+            double w[D];
+            Mat V;
+            heig(P.nr, Q, w, V);                              // ascending (util/misc.py:161-255 peig / leig)
+            if (algo == 1) {     // alt-min: C_k, the interference subspace (peig), and what it leaves out
+                for (int i = 0; i < P.nr; ++i) {
+                    for (int j = 0; j < P.nr - S.ns[k]; ++j) S.W[k].a[i][j] = V.a[i][P.nr - 1 - j];
+                    for (int j = 0; j < S.ns[k]; ++j) S.X[k].a[i][j] = V.a[i][j];
+                }
+            } else {             // min leakage (leig)
+                for (int i = 0; i < P.nr; ++i)
+                    for (int j = 0; j < S.ns[k]; ++j) S.W[k].a[i][j] = V.a[i][j];
+            }
         }
     }
 }
 
-__device__ void update_F(const Problem& P, State& S, int algo) {
-    Mat Fn[KM], Q, H, A;
-    if (algo == 1) {     // alternating minimisation (algorithms.py:1014-1058)
-        Mat Y[KM];
-        for (int k = 0; k < P.K; ++k) {
-            const int nc = P.nr - S.ns[k];
-            for (int i = 0; i < P.nr; ++i)
-                for (int j = 0; j < P.nr; ++j) {
-                    cd s = c0();
-                    for (int c = 0; c < nc; ++c) s = cadd(s, cmul(S.W[k].a[i][c], cconj(S.W[k].a[j][c])));
-                    Y[k].a[i][j] = mk<double>((i == j ? 1.0 : 0.0) - s.x, -s.y);
-                }
-        }
+__device__ void update_F(const Problem& P, State& S, int algo, bool& ok) {
+    Mat Fn[KM], H, A;
+    if (algo == 1 || algo == 2) {
+        // alternating minimisation (algorithms.py:1014-1058): the ns smallest eigenvectors of sum_k H_kl^H Y_k H_kl with
+        // Y_k = I - C_k C_k^H = X_k X_k^H; min leakage (:1180-1240): those of calc_Q_rev = sum_k H_kl^H W_k W_k^H H_kl.
+        // Both are A^H A of the stacked factor A = [X_k^H H_kl]_k (resp. W_k), and F_l is read from A's right singular
+        // vectors: the leakage is a squared singular value, and once it has sunk below eps |A|^2 the formed matrix keeps
+        // the span of a two-stream precoder but neither the split between its columns nor the `rel` stop that depends
+        // on them (tests/test_gpu_ia_general_envelope.py, the two-stream cases run for 80 iterations).
+        Tall T;
+        double w[D];
+        Mat V;
         for (int l = 0; l < P.K; ++l) {
-            mzero(Q);
+            int m = 0;
             for (int k = 0; k < P.K; ++k) {
                 if (k == l) continue;
                 P.block(k, l, H);
-                mm(Y[k], H, P.nr, P.nr, P.nt, A);              // Y_k H_kl
-                Mat T;
-                mm_h(H, A, P.nt, P.nr, P.nt, T);               // H_kl^H Y_k H_kl
-                for (int i = 0; i < P.nt; ++i)
-                    for (int j = 0; j < P.nt; ++j) Q.a[i][j] = cadd(Q.a[i][j], T.a[i][j]);
+                mm_h(algo == 1 ? S.X[k] : S.W[k], H, S.ns[k], P.nr, P.nt, A);     // X_k^H H_kl, ns_k x nt
+                for (int i = 0; i < S.ns[k]; ++i, ++m)
+                    for (int j = 0; j < P.nt; ++j) T.a[m][j] = A.a[i][j];
             }
-            for (int i = 0; i < P.nt; ++i) {                   // Hermitian by construction
-                Q.a[i][i].y = 0.0;
-                for (int j = i + 1; j < P.nt; ++j) Q.a[j][i] = cconj(Q.a[i][j]);
-            }
-            leig(P.nt, Q, S.ns[l], Fn[l]);
-            scale(Fn[l], P.nt, S.ns[l], 1.0 / fro(Fn[l], P.nt, S.ns[l]));
-        }
-    } else if (algo == 2) {   // min leakage (algorithms.py:1180-1240)
-        for (int k = 0; k < P.K; ++k) {
-            calc_Q_rev(P, S, k, Q);
-            leig(P.nt, Q, S.ns[k], Fn[k]);
+            hsvd_right(m, P.nt, T, w, V);
+            for (int i = 0; i < P.nt; ++i)
+                for (int j = 0; j < S.ns[l]; ++j) Fn[l].a[i][j] = V.a[i][j];
+            // alt-min normalises (:1050); min leakage stops at one stream in the reference (calc_Q_rev asserts,
+            // iabase.py:663), where the vector IS the unit-norm precoder; ns orthonormal columns carry ns times the user's
+            // power until they are scaled like every other F
+            if (algo == 1 || S.ns[l] > 1) scale(Fn[l], P.nt, S.ns[l], 1.0 / fro(Fn[l], P.nt, S.ns[l]));
         }
     } else {                  // max-SINR in the reverse network (algorithms.py:1265-1345, 1457-1480): every
         for (int k = 0; k < P.K; ++k) {   // "transmitter" j enters with power P / Ns_j per stream
@@ -342,9 +404,10 @@ __device__ void update_F(const Problem& P, State& S, int algo) {
                     B.a[i][i].x += P.nv;
                     rhs.a[i][0] = A.a[i][l];
                 }
-                solve(P.nt, B, rhs, 1);
+                ok = solve(P.nt, B, rhs, 1) && ok;
                 double nrm = 0.0;
                 for (int i = 0; i < P.nt; ++i) nrm += abs2(rhs.a[i][0]);
+                ok = ok && nrm > 0.0;
                 nrm = 1.0 / sqrt(nrm);
                 for (int i = 0; i < P.nt; ++i) Fn[k].a[i][l] = cscale(rhs.a[i][0], nrm);
             }
@@ -428,14 +491,14 @@ __device__ void solve_finalize(const Problem& P, State& S) {
 // Fc_first: precoders the FIRST receive-filter update builds its covariances from (null: S.F).
 __device__ int run_solver(const Problem& P, State& S, int algo, int max_iter, double rel, bool& ok,
                           const Mat* Fc_first = nullptr) {
-    update_W(P, S, algo, Fc_first ? Fc_first : S.F);
+    update_W(P, S, algo, Fc_first ? Fc_first : S.F, ok);
     int runned = 0;
     for (int it = 0; it < max_iter; ++it) {
         Mat Fo[KM];
         for (int k = 0; k < P.K; ++k) Fo[k] = S.F[k];
         ++runned;
-        update_F(P, S, algo);
-        update_W(P, S, algo, S.F);
+        update_F(P, S, algo, ok);
+        update_W(P, S, algo, S.F, ok);
         if (!diff_significant(P, S, Fo, rel)) break;
     }
     Mat H, A;
@@ -493,6 +556,7 @@ __device__ double finish(const Problem& P, const State& S, Mat* U, double (*sinr
             cap += log2(1.0 + sinr[k][l]);
         }
     }
+    if (!isfinite(cap)) ok = false;                           // a NaN or an unbounded SINR never leaves as a plain result
     return cap;
 }
 

@@ -36,6 +36,7 @@ extern "C" {
 int mcle_ia_solve_general(mcle_ctx* ctx, const mcle_ia_general_cfg* cfg, const void* d_bigH, const void* d_F_init,
                           void* d_F, void* d_U, double* d_sinr, double* d_capacity, uint32_t* d_iterations,
                           int32_t* d_ns, uint32_t* d_skipped, double* d_every_capacity, size_t batch) {
+    if (ctx) ctx->last_kernel[0] = 0;
     MCLE_REQUIRE(ctx != nullptr && cfg != nullptr && d_bigH != nullptr && d_F != nullptr && d_U != nullptr, "null argument");
     MCLE_REQUIRE(cfg->K >= 2 && cfg->K <= iag::KM, "K must be in [2, %d]", iag::KM);
     MCLE_REQUIRE(cfg->nr >= 1 && cfg->nr <= iag6::D && cfg->nt >= 1 && cfg->nt <= iag6::D,
@@ -73,6 +74,7 @@ int mcle_ia_solve_general(mcle_ctx* ctx, const mcle_ia_general_cfg* cfg, const v
         pp.select = cfg->stream_selection;
         pp.nv = cfg->noise_var;
         pp.rel = cfg->relative_factor;
+        ctx->set_kernel("ia_general<6> K=%d %dx%d", pp.K, pp.nr, pp.nt);
         hipLaunchKernelGGL(iag6::k_ia_general, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, ctx->stream, pp,
                            (const double2*)d_bigH, (const double2*)d_F_init, (double2*)d_F, (double2*)d_U, d_sinr,
                            d_capacity, d_iterations, d_ns, d_skipped, d_every_capacity, batch);
@@ -90,6 +92,7 @@ int mcle_ia_solve_general(mcle_ctx* ctx, const mcle_ia_general_cfg* cfg, const v
     pp.select = cfg->stream_selection;
     pp.nv = cfg->noise_var;
     pp.rel = cfg->relative_factor;
+    ctx->set_kernel("ia_general<4> K=%d %dx%d", pp.K, pp.nr, pp.nt);
     hipLaunchKernelGGL(iag::k_ia_general, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, ctx->stream, pp,
                        (const double2*)d_bigH, (const double2*)d_F_init, (double2*)d_F, (double2*)d_U, d_sinr,
                        d_capacity, d_iterations, d_ns, d_skipped, d_every_capacity, batch);

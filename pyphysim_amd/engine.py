@@ -1020,7 +1020,9 @@ class Engine:
         -- 'fix' / a captured random start -- or None for the 'svd' start.  select: None, 'greedy' (GreedStreamIASolver)
         or 'brute' (BruteForceStreamIASolver, always from 'svd').  -> dict of padded arrays: F [b, K, D, D] (nt x ns in the
         top-left corner), U = full_W_H [b, K, D, D] (ns x nr), sinr [b, K, D], capacity [b], iterations [b],
-        Ns [b, K], skipped [b]."""
+        Ns [b, K], skipped [b] (+ every_capacity [b, prod(Ns)] for 'brute').  Outside the envelope (include/mcle.h: K in
+        [2, 4], Nr, Nt in [1, 6], Ns[k] in [1, min(Nr, Nt)], max_iterations >= 1, noise_var >= 0, 'svd' and 'brute' with
+        Nr == Nt, at most 256 stream combinations) -> ValueError and last_kernel() == ''; else 'ia_general<D> K=.. NrxNt'."""
         D = 4 if max(int(nr), int(nt)) <= 4 else 6
         H = np.ascontiguousarray(big_H, dtype=np.complex128)
         if H.ndim == 2:
