@@ -105,7 +105,10 @@ int mcle_ctx_device_info(mcle_ctx* ctx, int* n_cu, int* lds_bytes, char* name, i
  *                                             the time-domain form; suffix "/w2" = registers bounded for two wavefronts per SIMD where
  *                                             three is the default (NW = 2: f64_threads 262, NW = 4: 264; NW = 8 has the one bound);
  *                                             suffix "/a" (after "/freq" only) = the ownership map of rounds 6 - 9, wavefront = time
- *                                             class and lane row = antenna (f64_threads 266); no suffix = ownership by lane row
+ *                                             class and lane row = antenna (f64_threads 266); suffix "/x" (after "/freq" only) = ownership
+ *                                             by lane row with the exchange by re / im planes of rounds 10 - 19 asked for (f64_threads
+ *                                             267), suffix "/h" = with the exchange in complex halves asked for (268); no suffix =
+ *                                             ownership by lane row, the exchange the default picks (halves at 1024 / 2048, planes at 512)
  *   "mimo_ofdm_fw<NA> f64|f32 w<WPS>"          full-wave at 256 points, NA x NA antennas, wavefronts per SIMD the registers are bounded for
  *   "mimo_ofdm_qw w<WPS>"                      quarter-wave (complex128, 1024, 4x4)
  *   "mimo_ofdm_planar<N,NT,NR> f64|f32 ah<AH> w<WPS> v<VARIANT>"   the planar family: antennas per thread, wavefronts per SIMD, variant
@@ -162,7 +165,7 @@ enum {
                                       csrc/pipeline_mimo_fw.hip, one realization per wavefront) / the half-wave kernel (512:
                                       csrc/pipeline_mimo_pw.hip, two wavefronts per realization), both with channel AND decode on
                                       v_mfma_f64_4x4x4; 262 = bounded for two wavefronts per SIMD; 261 = the planar radix-4 form of
-                                      rounds 3-5 (in fact any value but 0 / 260 / 262; at 512 and 2048 any but 0 / 260 / 262 / 265 / 266); both
+                                      rounds 3-5 (in fact any value but 0 / 260 / 262; at 512 and 2048 any but 0 / 260 / 262 / 265 - 268); both
                                       arithmetics at 256 (complex64: 0 = two wavefronts per SIMD, 262 = three); (256, 2x2): the full-wave
                                       kernel with two realizations per wavefront, and with 261 or outside the envelope the GENERIC
                                       kernel -- the planar family has no (256, 2x2) kernel, the generic one is faster there;
@@ -178,9 +181,16 @@ enum {
                                       samples of a Philox noise block in one wavefront, their words exchanged in registers, one
                                       workgroup barrier fewer; 266 = the map of rounds 6 - 9 (a wavefront owns one time class of
                                       all antennas, the words go through LDS) at all three sizes, same counts, tag suffix "/a".
+                                      Since round 20 the wavefronts of a realization exchange their partial spectra as complex values
+                                      in two halves, each lane refilling the LDS slots it has just read -- one workgroup barrier
+                                      fewer; 267 = ownership by lane row with the exchange by re / im planes of
+                                      rounds 10 - 19 (barrier B3) at all three sizes, same counts, tag suffix "/x": the witness.
+                                      The default takes the exchange in complex halves at 1024 and 2048 points and keeps the planes
+                                      at 512, where the halves were not faster in every run; 268 = the exchange in complex halves
+                                      at all three sizes, same counts, tag suffix "/h".
                                       (1024, Nt < 4, Nr = 4), either arithmetic: 0 = the radix-16 form, any other value the radix-4 one.
                                       mcle_ctx_last_kernel names the kernel that served the call -- for the part-wave kernel the size
-                                      and the form, "mimo_ofdm_pw<NW>/freq" or ".../time" (+ "/w2" at the two-wavefront bound, + "/a" for 266); the
+                                      and the form, "mimo_ofdm_pw<NW>/freq" or ".../time" (+ "/w2" at the two-wavefront bound, + "/a" for 266, "/x" for 267, "/h" for 268); the
                                       whole grammar is listed there. */
     MCLE_OPT_BD_RUNTIME_SOLVE = 9, /* 1: the block-diagonalisation pipeline solves with the run-time-sized routine (private
                                       arrays in scratch) also where the compile-time-sized one (K nr <= 6) applies */

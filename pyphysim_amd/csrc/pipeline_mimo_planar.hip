@@ -583,9 +583,9 @@ static int run_mimo_ofdm_planar_t(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, 
         if constexpr (F64) {
             // round 6: the HALF-WAVE / EIGHTH-WAVE kernel (pipeline_mimo_pw.hip, NW = 2 / 8).  MCLE_OPT_F64_THREADS = 261 (and, at 2048,
             // 512 / 1024): the planar radix-4 forms; 265: the part-wave kernel in its time-domain form; 266: its default form with
-            // the ownership map of rounds 6 - 9.
+            // the ownership map of rounds 6 - 9; 267: ownership by lane row with the exchange by re / im planes of rounds 10 - 19 (the default at 512); 268: the exchange in complex halves (the default at 2048).
             const long long thr = ctx->opt[MCLE_OPT_F64_THREADS];
-            if (thr == 0 || thr == 260 || thr == 262 || thr == 265 || thr == 266) {
+            if (thr == 0 || thr == 260 || thr == 262 || thr == 265 || thr == 266 || thr == 267 || thr == 268) {
                 const int rq = run_mimo_ofdm_pw(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
                 if (rq != MCLE_E_UNSUPPORTED) return rq;
             }
@@ -598,9 +598,10 @@ static int run_mimo_ofdm_planar_t(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, 
                 // profiles/r06/pw_ab.log).  MCLE_OPT_F64_THREADS = 263: the same, explicit; 264: registers bounded for two wavefronts
                 // per SIMD; 260 / 262: the quarter-wave kernel of pipeline_mimo_qw.hip (VALU decode, four bins per thread).
                 // Since round 7 it adds the signal AFTER the receive transform (no transmit transform: DESIGN.md 5.14); 265: its
-                // time-domain form of round 6; 266: the default form with the ownership map of rounds 6 - 9.
+                // time-domain form of round 6; 266: the default form with the ownership map of rounds 6 - 9;
+                // 267: ownership by lane row with the exchange by re / im planes of rounds 10 - 19; 268: the exchange in complex halves, explicit.
                 const long long thr = ctx->opt[MCLE_OPT_F64_THREADS];
-                if (thr == 0 || thr == 263 || thr == 264 || thr == 265 || thr == 266) {
+                if (thr == 0 || thr == 263 || thr == 264 || thr == 265 || thr == 266 || thr == 267 || thr == 268) {
                     const int rq = run_mimo_ofdm_pw(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
                     if (rq != MCLE_E_UNSUPPORTED) return rq;
                 }

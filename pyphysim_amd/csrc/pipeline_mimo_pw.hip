@@ -31,6 +31,9 @@
 // row rho of wavefront w owns the pair f = NW antenna + class = 4 w + rho, so the two samples of a Philox NOISE block sit sixteen lanes
 // apart in ONE wavefront and their words change rows in registers -- no LDS round trip, no barrier B1.  The map of
 // the text above (wavefront = class, row = antenna) stays as ROWS = false, option f64_threads = 266: the A/B partner.
+// Round 20: at 1024 and 2048 points the exchange between the wavefronts carries COMPLEX values in two halves (template parameter
+// XCH = true), each lane refilling the slots it has just read: workgroup barrier B3 is not issued.  512 points and
+// option f64_threads = 267 keep the re / im planes; 268 asks for the halves at every size.
 #include "mimo_planar_common.hpp"
 #include "walk_f64.hpp"
 
@@ -196,7 +199,24 @@ __device__ __forceinline__ void pw_first_stage(const unsigned char* lab_row, con
 // f of the planes (272 doubles each, + 16 for an odd antenna: the rows r, r + 1 of one reading half-wave land on the two halves of
 // the bank row); the reader of antenna r takes class jj from slice NW r + jj.  Every floating-point operation and its operands are
 // those of ROWS = false (option f64_threads = 266) -- only the wavefront and the lane where it runs moved.
-template <int NW, int DEC, int WPS, bool TD = false, int ABL = 0, bool ROWS = !TD>
+// XCH = true (what the default form by lane row runs at 1024 and 2048 points since round 20): THE EXCHANGE IN COMPLEX HALVES.  The sixteen
+// elements of a lane go through LDS as complex values (16-byte stores and loads) in two halves by uu instead of as re and im planes:
+// phase A carries uu < UU / 2 of every reader, phase B the rest.  A slice (272 doubles = 136 slots of 16 bytes) holds 128 values per
+// phase: the writer (wavefront w, row rho) puts element k' = g + 16 (UU jw + uu) into slot g + 16 ((UU / 2) jw + uu) of slice 4 w + rho,
+// and behind B2 the reader (wavefront jw, row r) takes class jj from slice NW r + jj.  Every phase-A slot is read by exactly ONE lane,
+// and that lane stores its own eight phase-B values into the eight slots it has just read -- the value for (reader wavefront jw',
+// uu') into the slot it read for (jj = jw', uu' - UU / 2).  A wavefront's LDS operations complete in issue order, so the store stands
+// behind the load of the same slot and nobody else touches the slot in between: BARRIER B3 IS NOT ISSUED.  Behind B4 the reader finds
+// (antenna r, class jj), which the pair f = NW r + jj = 4 w' + rho' computed, in slice NW rho' + jw at g + 16 ((UU / 2) w' + uu - UU / 2).
+// No shift for odd antennas: the rows r, r + 1 of one 16-lane group of a 16-byte read lie a multiple of 256 bytes apart in both
+// phases, sixteen consecutive slots each (tests/test_pw_exchange_layout.py replays all of it, bank conflicts included).
+// BARRIER B5 behind the draw (round 20, item 2; NOT in the default build: it measured 0.1 ms per 2^20 realizations SLOWER than B5 at
+// the top, profiles/r20/pw_exchange_ab.log): with XCH, -DMCLE_PW_LATE_B5 moves B5 from the top of the symbol to the first store into
+// the planes (the transposition behind pass 2') -- labels, records and the draw own nothing another wavefront still reads (DESIGN.md
+// 5.28 has the argument per LDS object), so decode, S0a and the whole draw run without a barrier between them.
+// XCH = false (option f64_threads = 267, tag suffix "/x") is the exchange by re / im planes with B3: the witness.  ROWS = false, TD
+// and the ABL builds keep it as well.
+template <int NW, int DEC, int WPS, bool TD = false, int ABL = 0, bool ROWS = !TD, bool XCH = ROWS && !TD>
 __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp, ModemParams<double> mp, uint64_t seed, uint64_t first,
                                                                    uint64_t count, const double2* __restrict__ g_tw,
                                                                    const double2* __restrict__ g_recs, mcle_counters* counters,
@@ -206,6 +226,13 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
     constexpr int kLabStride = pw_lab_stride<NW>();
     static_assert(NW == 2 || NW == 4 || NW == 8, "wavefronts per realization");
     static_assert(!(TD && ROWS), "the time-domain form keeps the map wavefront = class");
+    static_assert(!XCH || (ROWS && ABL == 0), "the exchange in complex halves belongs to the default form by lane row");
+    constexpr bool kAhead = ROWS && ABL == 0;
+#ifdef MCLE_PW_LATE_B5
+    constexpr bool kLateB5 = XCH && kAhead;
+#else
+    constexpr bool kLateB5 = false;
+#endif
     constexpr int kLogNW = NW == 2 ? 1 : NW == 4 ? 2 : 3;
     extern __shared__ __attribute__((aligned(16))) char pw_smem[];
     // Round 8: everything of a FIXED size is a static array -- the Box-Muller tables, the label rows, the records, the partial counts, the
@@ -261,7 +288,10 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
         const cx<T>* s_G = s_H + NT * NR;                                   // [NT][NR]
         unsigned se = 0, be = 0;
         for (int os = 0; os < pp.n_ofdm_sym; ++os) {
-            if (it > 0 || os > 0) __syncthreads();          // B5: the previous symbol's exchange planes and labels have been read
+            // B5: the previous symbol's exchange planes and labels have been read (kLateB5: in front of the first store into the planes)
+            if constexpr (!kLateB5) {
+                if (it > 0 || os > 0) __syncthreads();
+            }
             // The loop comes back here with scalar loads of the decode on the books, and a scalar load returns out of order: the first
             // LDS wait behind it can only be lgkmcnt(0), which in the pipelined draw would wait for block 1's table reads three
             // instructions behind their issue.  Retire them here, behind the barrier, where nothing is in flight: the draw's first wait
@@ -480,6 +510,15 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                 const int a = ln >> 4, g = ln & 15;
                 const int wbase = pw_slot(a, g), rbase = pw_slot(a, 16 * g);
                 T xr[16];
+                // B5 (kLateB5): this is the symbol's first store into a plane, and the other wavefronts' phase-B loads of the previous
+                // symbol read this one -- S0a, the draw and pass 2' above touch nothing that the previous symbol still reads
+                // (the sixteen samples are pinned in front of the branch: left alone the compiler sinks every cn_finish of the draw below the
+                //  conditional barrier, keeps all sixteen fetched samples alive up to it and spills a hundred registers)
+                if constexpr (kLateB5) {
+#pragma unroll
+                    for (int c = 0; c < 16; ++c) asm volatile("" : "+v"(v[c].x), "+v"(v[c].y));
+                    if (it > 0 || os > 0) __syncthreads();
+                }
 #pragma unroll
                 for (int c = 0; c < 16; ++c) s_mine[rbase + c] = v[c].x;
                 walk_wave_order();
@@ -505,11 +544,11 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
             // ---- the exchange: Y_j[k'] of receive antenna r (lane (r, g), register u: k' = g + 16 u) -> plane j at r 272 + k', re then
             //      im; lane (r, g) of wavefront jw reads the NW partial transforms of ITS k' = g + 16 (UU jw + uu), antenna r only ----
             T er[NW][UU], ei[NW][UU];
+            cx<T> ez[NW][UU];                                                     // (XCH) the same values as complex numbers
             // Round 17 (default form by lane row): what the code behind B4 reads and the exchange does not write -- the lane's label
             // row, H[h mod 4][a], G[h mod 4][r], the last stage's twiddles of uu = 0 -- is read BEFORE the wait at B4, so its latency
             // runs while the wavefront stands at the barrier; the twiddles of uu + 1 are then issued ahead of the butterflies of uu.
             // The same loads, the same values, another place.
-            constexpr bool kAhead = ROWS && ABL == 0;
             constexpr uint32_t kTwBytes = (uint32_t)sizeof(cx<T>);                // one twiddle table entry; 16 entries from uu to uu + 1
             uint32_t kp0 = 0;
             // W_N^(m kp), kp = kp0 + 16 uu: table m is ONE lane offset 16 m kp0 bytes behind the (scalar) table pointer and uu only moves
@@ -523,7 +562,60 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
             cx<T> twb[2][NW - 1];                                                 // (kAhead) twiddles of uu in twb[uu & 1]
             uint4 lab_ahead = make_uint4(0, 0, 0, 0);
             cx<T> hA_ahead = mk<T>(0, 0), gA_ahead = mk<T>(0, 0);
-            {
+            if constexpr (XCH) {
+                const int ln = opaque(lane);
+                const int r = ln >> 4, g = ln & 15;
+                constexpr int UH = UU / 2, kSl = 272 / 2;                           // uu per phase; 16-byte slots per slice
+                cx<T>* s_X = reinterpret_cast<cx<T>*>(s_R);
+                const int wA = (4 * j + r) * kSl + g;                              // phase A store: slice 4 j + r, slot g + 16 (UH jw + uu)
+                const int rA = NW * r * kSl + g + 16 * UH * j;                     // phase A load (+ jj slices, + 16 uu) = phase B store
+                // phase B load: (antenna r, class jj) was computed by the pair f = NW r + jj = 4 w' + rho' and lies in slice NW rho' + j
+                // at g + 16 (UH w' + uu - UH).  NW = 2: w' = r >> 1, rho' = 2 (r & 1) + jj; NW = 4, 8: w' = (NW / 4) r + (jj >> 2), rho' = jj & 3
+                const int rB = NW == 2 ? (4 * (r & 1) + j) * kSl + g + 16 * UH * (r >> 1) : j * kSl + g + 16 * UH * (NW / 4) * r;
+                r16_wave_sync();                               // (my own reads of the transposition are done)
+                // THE ROUNDINGS OF PASS 1' ARE KEPT BY KEEPING ITS BASIC BLOCKS.  -ffp-contract=fast fuses a product and a sum only inside one
+                // basic block.  In the re / im exchange the real parts were consumed in front of the branch of account_prev() and the
+                // imaginary parts behind it: the compiler sank the last imaginary sums of the pass below that branch, and two of them
+                // -- y h - x h of the roots (1 -/+ i) / sqrt 2 -- stayed a v_mul_f64 and a v_add_f64 there.  With all sixteen values
+                // consumed in one block they become v_fma_f64: 2 of 1 553 static f64 instructions, another last bit in the noise
+                // spectrum.  So the real parts are pinned here, the previous realization is accounted (one branch, thread 0), and the
+                // imaginary parts are pinned behind it: kernel_census.py counts the parent's f64 instructions opcode for opcode.
+                // account_prev() in front of B2 is safe: it runs at os = 0, it > 0 only, where this symbol's B5 -- at the top or in
+                // front of the transposition -- has been passed, i.e. every wavefront has left the previous realization and its
+                // s_part entries; s_part[buf ^ 1] and the flag of s_rec[buf ^ 1] are next written a realization later.
+#pragma unroll
+                for (int u = 0; u < 16; ++u) asm volatile("" : "+v"(v[u].x));
+                account_prev();
+#pragma unroll
+                for (int u = 0; u < 16; ++u) asm volatile("" : "+v"(v[u].y));
+#pragma unroll
+                for (int jw = 0; jw < NW; ++jw)
+#pragma unroll
+                    for (int uu = 0; uu < UH; ++uu) s_X[wA + 16 * (UH * jw + uu)] = v[UU * jw + uu];
+                __syncthreads();                               // B2
+#pragma unroll
+                for (int jj = 0; jj < NW; ++jj)
+#pragma unroll
+                    for (int uu = 0; uu < UH; ++uu) ez[jj][uu] = s_X[rA + jj * kSl + 16 * uu];
+                // no B3: each slot is refilled by the lane that has just read it, behind that read in the wavefront's LDS queue
+#pragma unroll
+                for (int jw = 0; jw < NW; ++jw)
+#pragma unroll
+                    for (int uu = UH; uu < UU; ++uu) s_X[rA + jw * kSl + 16 * (uu - UH)] = v[UU * jw + uu];
+                kp0 = (uint32_t)opaque((ln & 15) + 16 * UU * j);
+#pragma unroll
+                for (int m = 1; m < NW; ++m) twb[0][m - 1] = tw_at(m, 0);
+                lab_ahead = *reinterpret_cast<const uint4*>(s_lab + ln * kLabStride + 16 * j);
+                hA_ahead = s_H[(ln & 3) * NT + (ln >> 4)];
+                gA_ahead = s_G[(ln & 3) * NR + (ln >> 4)];
+                __syncthreads();                               // B4
+#pragma unroll
+                for (int jj = 0; jj < NW; ++jj) {
+                    const int off = NW == 2 ? 2 * jj * kSl : (jj & 3) * NW * kSl + 16 * UH * (jj >> 2);
+#pragma unroll
+                    for (int uu = UH; uu < UU; ++uu) ez[jj][uu] = s_X[rB + off + 16 * (uu - UH)];
+                }
+            } else {
                 const int ln = opaque(lane);
                 const int r = ln >> 4, g = ln & 15;
                 // ROWS: my row r carries the pair f = 4 j + r -> slice f = row r of my plane, + 16 for an odd antenna; antenna r's
@@ -563,6 +655,10 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                 const int ln = opaque(lane);
                 if constexpr (!kAhead) kp0 = (uint32_t)opaque((ln & 15) + 16 * UU * j);
                 // kAhead: the twiddles of uu were loaded one step ahead (uu = 0: before B4), those of uu + 1 go out before the butterflies of uu
+                auto ex = [&](int jj, int uu) {
+                    if constexpr (XCH) return ez[jj][uu];
+                    else return mk<T>(er[jj][uu], ei[jj][uu]);
+                };
                 auto tw_of = [&](int m, int uu) {
                     if constexpr (kAhead) return twb[uu & 1][m - 1];
                     else return tw_at(m, uu);
@@ -578,18 +674,18 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                     }
                     if constexpr (NW == 4) {
                         const cx<T> w1 = tw_of(1, uu), w2 = tw_of(2, uu), w3 = tw_of(3, uu);
-                        const cx<T> u0 = mk<T>(er[0][uu], ei[0][uu]);
-                        const cx<T> u1 = cmul(mk<T>(er[1][uu], ei[1][uu]), w1);
-                        const cx<T> u2 = cmul(mk<T>(er[2][uu], ei[2][uu]), w2);
-                        const cx<T> u3 = cmul(mk<T>(er[3][uu], ei[3][uu]), w3);
+                        const cx<T> u0 = ex(0, uu);
+                        const cx<T> u1 = cmul(ex(1, uu), w1);
+                        const cx<T> u2 = cmul(ex(2, uu), w2);
+                        const cx<T> u3 = cmul(ex(3, uu), w3);
                         CxOps<T>::template bfly4<false>(u0, u1, u2, u3, v[4 * uu], v[4 * uu + 1], v[4 * uu + 2], v[4 * uu + 3]);
                     } else if constexpr (NW == 8) {
                         // Y_q = E_q + w'^q O_q, Y_(q + 4) = E_q - w'^q O_q, E / O = the 4-point forward transforms of the even / odd
                         // partial transforms, w' = e^(-2 pi i / 8)
                         cx<T> x[8];
-                        x[0] = mk<T>(er[0][uu], ei[0][uu]);
+                        x[0] = ex(0, uu);
 #pragma unroll
-                        for (int jj = 1; jj < 8; ++jj) x[jj] = cmul(mk<T>(er[jj][uu], ei[jj][uu]), tw_of(jj, uu));
+                        for (int jj = 1; jj < 8; ++jj) x[jj] = cmul(ex(jj, uu), tw_of(jj, uu));
                         cx<T> E[4], O[4];
                         CxOps<T>::template bfly4<false>(x[0], x[2], x[4], x[6], E[0], E[1], E[2], E[3]);
                         CxOps<T>::template bfly4<false>(x[1], x[3], x[5], x[7], O[0], O[1], O[2], O[3]);
@@ -603,8 +699,8 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                         v[8 * uu + 2] = cadd(E[2], t2); v[8 * uu + 6] = csub(E[2], t2);
                         v[8 * uu + 3] = cadd(E[3], t3); v[8 * uu + 7] = csub(E[3], t3);
                     } else {
-                        const cx<T> u0 = mk<T>(er[0][uu], ei[0][uu]);
-                        const cx<T> u1 = cmul(mk<T>(er[1][uu], ei[1][uu]), tw_of(1, uu));
+                        const cx<T> u0 = ex(0, uu);
+                        const cx<T> u1 = cmul(ex(1, uu), tw_of(1, uu));
                         v[2 * uu] = cadd(u0, u1);
                         v[2 * uu + 1] = csub(u0, u1);
                     }
@@ -713,7 +809,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
     }
 }
 
-template <int NW, int WPS, bool TD = false, int ABL = 0, bool ROWS = !TD>
+template <int NW, int WPS, bool TD = false, int ABL = 0, bool ROWS = !TD, bool XCH = ROWS && ABL == 0>
 static int launch_mimo_ofdm_pw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
                                mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit) {
     using T = double;
@@ -729,11 +825,11 @@ static int launch_mimo_ofdm_pw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uin
     const size_t dyn = (size_t)NW * kPwPlane * sizeof(T) + 2 * tab_len * sizeof(cx<T>);      // planes + the two constellation tables
     const size_t lds = dyn + pw_static_lds<NW>();                                             // + the kernel's static arrays
     MCLE_REQUIRE(lds + 512 <= (size_t)160 * 1024, "part-wave MIMO-OFDM kernel: %zu B of LDS do not fit", lds);
-    auto kern = k_run_mimo_ofdm_pw<NW, WDEC_SLICER, WPS, TD, ABL, ROWS>;
+    auto kern = k_run_mimo_ofdm_pw<NW, WDEC_SLICER, WPS, TD, ABL, ROWS, XCH>;
     switch (dec) {
-        case WDEC_QAM_CERT: kern = k_run_mimo_ofdm_pw<NW, WDEC_QAM_CERT, WPS, TD, ABL, ROWS>; break;
-        case WDEC_QUAD_CERT: kern = k_run_mimo_ofdm_pw<NW, WDEC_QUAD_CERT, WPS, TD, ABL, ROWS>; break;
-        case WDEC_AXIS4_CERT: kern = k_run_mimo_ofdm_pw<NW, WDEC_AXIS4_CERT, WPS, TD, ABL, ROWS>; break;
+        case WDEC_QAM_CERT: kern = k_run_mimo_ofdm_pw<NW, WDEC_QAM_CERT, WPS, TD, ABL, ROWS, XCH>; break;
+        case WDEC_QUAD_CERT: kern = k_run_mimo_ofdm_pw<NW, WDEC_QUAD_CERT, WPS, TD, ABL, ROWS, XCH>; break;
+        case WDEC_AXIS4_CERT: kern = k_run_mimo_ofdm_pw<NW, WDEC_AXIS4_CERT, WPS, TD, ABL, ROWS, XCH>; break;
         default: break;
     }
     MCLE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
@@ -743,8 +839,13 @@ static int launch_mimo_ofdm_pw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uin
     if (per_cu > by_waves) per_cu = by_waves;
     const uint64_t resident = (uint64_t)ctx->n_cu * per_cu;
     // which form served the call (mcle_ctx_last_kernel); "/w2": the two-wavefront register bound where three is the default (NW = 2, 4);
-    // "/a": the default form with the ownership map of rounds 6 - 9 (wavefront = class, row = antenna)
-    ctx->set_kernel("mimo_ofdm_pw<%d>/%s%s%s", NW, TD ? "time" : "freq", WPS == (NW == 8 ? 2 : 3) ? "" : "/w2", !TD && !ROWS ? "/a" : "");
+    // "/a": the default form with the ownership map of rounds 6 - 9 (wavefront = class, row = antenna); "/x": ownership by lane row
+    // with the exchange by re / im planes of rounds 10 - 19 (barrier B3) ASKED FOR (267), "/h": the exchange in complex halves asked
+    // for (268) -- what the default picks per size carries no suffix
+    const long long asked = ctx->opt[MCLE_OPT_F64_THREADS];
+    static_assert(XCH ? ROWS && ABL == 0 : true, "the exchange in complex halves: default form by lane row only");
+    ctx->set_kernel("mimo_ofdm_pw<%d>/%s%s%s", NW, TD ? "time" : "freq", WPS == (NW == 8 ? 2 : 3) ? "" : "/w2",
+                    !TD && !ROWS ? "/a" : asked == 267 ? "/x" : asked == 268 ? "/h" : "");
     const uint64_t kSlice = 1ull << 20;          // realizations per record kernel + link kernel pair (553 MB of records; 2^18: three more tails per bench step, -0.6 %)
     const uint64_t slice = count < kSlice ? count : kSlice;
     void* recs = nullptr;
@@ -775,7 +876,10 @@ int run_mimo_ofdm_pw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed
         if (walk_dec_kind(ctx, mp) == WDEC_GENERIC) return MCLE_E_UNSUPPORTED;     // no certificate: the planar kernel's candidate grid
     }
     // MCLE_OPT_F64_THREADS: 265 = the time-domain form (three wavefronts per SIMD); 262 / 264 = two wavefronts per SIMD; 266 = the
-    // default form with the ownership map of rounds 6 - 9 (noise words through LDS, barrier B1); the ablations of the
+    // default form with the ownership map of rounds 6 - 9 (noise words through LDS, barrier B1); 267 = ownership by lane row with the
+    // exchange by re / im planes (barrier B3: the witness of round 20, and what the default still is at 512 points, where the
+    // exchange in complex halves was not faster in every run -- DESIGN.md 5.28); 268 = the exchange in complex halves at all three
+    // sizes (the default at 1024 and 2048); the ablations of the
     // MCLE_EXPERIMENTS builds (option f64_variant) apply to the time-domain form and to the default form with its default map
     const bool two = ctx->opt[MCLE_OPT_F64_THREADS] == 262 || ctx->opt[MCLE_OPT_F64_THREADS] == 264;
     const bool td = ctx->opt[MCLE_OPT_F64_THREADS] == 265;
@@ -783,6 +887,16 @@ int run_mimo_ofdm_pw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed
         if (cfg->fft_size == 2048) return launch_mimo_ofdm_pw<8, 2, false, 0, false>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
         if (cfg->fft_size == 512) return launch_mimo_ofdm_pw<2, 3, false, 0, false>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
         return launch_mimo_ofdm_pw<4, 3, false, 0, false>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
+    }
+    if (ctx->opt[MCLE_OPT_F64_THREADS] == 268) {
+        if (cfg->fft_size == 2048) return launch_mimo_ofdm_pw<8, 2, false, 0, true, true>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
+        if (cfg->fft_size == 512) return launch_mimo_ofdm_pw<2, 3, false, 0, true, true>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
+        return launch_mimo_ofdm_pw<4, 3, false, 0, true, true>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
+    }
+    if (ctx->opt[MCLE_OPT_F64_THREADS] == 267) {
+        if (cfg->fft_size == 2048) return launch_mimo_ofdm_pw<8, 2, false, 0, true, false>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
+        if (cfg->fft_size == 512) return launch_mimo_ofdm_pw<2, 3, false, 0, true, false>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
+        return launch_mimo_ofdm_pw<4, 3, false, 0, true, false>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
     }
     if (cfg->fft_size == 2048) {     // eight wavefronts = 512 threads: one workgroup per CU (86 KiB of LDS), two wavefronts per SIMD
         return td ? launch_mimo_ofdm_pw<8, 2, true>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit)
@@ -805,8 +919,9 @@ int run_mimo_ofdm_pw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed
     if (cfg->fft_size == 512) {
         MCLE_PW_ABLS(2)
         if (td) return launch_mimo_ofdm_pw<2, 3, true>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-        return two ? launch_mimo_ofdm_pw<2, 2>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit)
-                   : launch_mimo_ofdm_pw<2, 3>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
+        // (512 points keep the exchange by re / im planes: profiles/r20/f64_family_rates.json)
+        return two ? launch_mimo_ofdm_pw<2, 2, false, 0, true, false>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit)
+                   : launch_mimo_ofdm_pw<2, 3, false, 0, true, false>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
     }
     MCLE_PW_ABLS(4)
 #undef MCLE_PW_ABLS

@@ -11,7 +11,7 @@ counted by class.  The class follows from the opcode's PREFIX alone (no list of 
 The count is static: a section is the TEXT between two barriers in layout order, whichever branches inside it are hot -- the
 dynamic figures are rocprofv3's SQ_INSTS_* (profiles/<round>/c4_f64_pmc_summary.json).  Runs without a GPU.
 
-usage: python scripts/kernel_census.py [--source pipeline_mimo_pw.hip] [--kernel 'k_run_mimo_ofdm_pw<4, 2, 3, false, 0, true>'] [--top N]
+usage: python scripts/kernel_census.py [--source pipeline_mimo_pw.hip] [--kernel 'k_run_mimo_ofdm_pw<4, 2, 3, false, 0, true, true>'] [--top N]
        (--top N adds the N most frequent opcodes of every section; --keep FILE keeps the kernel's assembly)"""
 import argparse
 import collections
@@ -75,7 +75,7 @@ def kernel_body(asm, want):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--source", default="pipeline_mimo_pw.hip")
-    ap.add_argument("--kernel", default="k_run_mimo_ofdm_pw<4, 2, 3, false, 0, true>")
+    ap.add_argument("--kernel", default="k_run_mimo_ofdm_pw<4, 2, 3, false, 0, true, true>")
     ap.add_argument("--top", type=int, default=0)
     ap.add_argument("--define", action="append", default=[])
     ap.add_argument("--keep", help="write the kernel's assembly to this file")

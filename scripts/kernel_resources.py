@@ -39,7 +39,8 @@ DEFAULT = [
     #  also for 2 x 2; the planar kernels below serve everything outside that envelope)
     # (round 7: pw<NW, decision form, wavefronts per SIMD, time-domain form, 0>: the default adds the signal after the receive transform)
     # (round 10: pw<..., 0, ownership by lane row>: true is the default form's default)
-    r"k_run_mimo_ofdm_pw<[24], [1-4], 3, false, 0, true>", r"k_run_mimo_ofdm_pw<8, [1-4], 2, false, 0, true>", r"k_run_mimo_ofdm_fw<[24], [1-4], 3, 0>",
+    # (round 20: pw<..., ownership by lane row, exchange in complex halves>: the default at 1024 and 2048 points)
+    r"k_run_mimo_ofdm_pw<2, [1-4], 3, false, 0, true, false>", r"k_run_mimo_ofdm_pw<4, [1-4], 3, false, 0, true, true>", r"k_run_mimo_ofdm_pw<8, [1-4], 2, false, 0, true, true>", r"k_run_mimo_ofdm_fw<[24], [1-4], 3, 0>",
     r"k_run_mimo_ofdm_planar<double, 1024, [1-4], 4, 4, 2, 12>", r"k_run_mimo_ofdm_planar<float, 1024, [1-4], 4, 4, 4, 4>",
     # (last day of round 6: complex64 at 256 points, and at 512 with two receive antennas, two more wavefronts per SIMD than the table)
     r"k_run_mimo_ofdm_planar<double, 256, [12], 2, 2, 2, 0>", r"k_run_mimo_ofdm_planar<double, 256, [1-3], 3, 3, 2, 0>",

@@ -12,7 +12,7 @@ load whose covering wait lies behind the section's closing barrier is listed wit
 
 The count is static and in layout order, as the census is: a branch inside a section is read straight through.
 
-usage: python scripts/wait_distance.py [--source pipeline_mimo_pw.hip] [--kernel 'k_run_mimo_ofdm_pw<4, 2, 3, false, 0, true>']
+usage: python scripts/wait_distance.py [--source pipeline_mimo_pw.hip] [--kernel 'k_run_mimo_ofdm_pw<4, 2, 3, false, 0, true, true>']
                                        [--list SECTION]    (every load of that section, not only the summary)"""
 import argparse
 import os
@@ -81,7 +81,7 @@ def distances(sec):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--source", default="pipeline_mimo_pw.hip")
-    ap.add_argument("--kernel", default="k_run_mimo_ofdm_pw<4, 2, 3, false, 0, true>")
+    ap.add_argument("--kernel", default="k_run_mimo_ofdm_pw<4, 2, 3, false, 0, true, true>")
     ap.add_argument("--define", action="append", default=[])
     ap.add_argument("--list", type=int, action="append", default=[], help="list every load of this section")
     args = ap.parse_args()
