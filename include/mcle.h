@@ -721,6 +721,40 @@ int mcle_ia_solve_general(mcle_ctx* ctx, const mcle_ia_general_cfg* cfg, const v
                           void* d_F, void* d_U, double* d_sinr, double* d_capacity, uint32_t* d_iterations,
                           int32_t* d_ns, uint32_t* d_skipped, double* d_every_capacity, size_t batch);
 
+/* ---- the IA link on general geometries, fused (apps/ia/simulate_ia.py:94-245 with Nr, Nt, Ns as parameters;
+ *      apps/ia/IA_Results_NrxNt(Ns).py: K = 3, 5 x 3, Ns = 2; apps/ia/simulate_greedy_ia.py: 3 x 3, Ns = 3 under the greedy
+ *      wrapper, its 'NoPathLoss' scenario = this link with P = 1, noise_var = 1 / SNR).  Per realization: draw big_H and -- for
+ *      MCLE_IA_INIT_GIVEN, which here means "drawn on chip" as in mcle_run_ia -- the random start (randomizeF, iabase.py:538-540);
+ *      solve with the kernel of mcle_ia_solve_general (stream_selection 0 / 1 / 2 included: the solution is bit-identical to
+ *      the operator's on the same inputs); send n_symbols per KEPT stream at unit power per user; add noise of variance
+ *      cfg->noise_var; apply full_W_H; demodulate; count.
+ * cfg: the envelope and the refusals of mcle_ia_solve_general, word for word; additionally n_symbols >= 1, a constellation of
+ *      M <= 256 and a known demod_method.  count = 0 returns MCLE_OK and launches nothing; nothing is written on a refusal.
+ * Draws (mcle-philox-v1, realization index = subsequence):
+ *   stream 2 (channel)  big_H[i][c], row-major over [K nr][K nt]: CN sample i K nt + c
+ *   stream 3 (start)    F_k[i][j] (nt x ns[k], the CONFIGURED ns): CN sample nt sum_{k' < k} ns[k'] + i ns[k] + j, then the
+ *                       matrix is divided by its Frobenius norm
+ *   stream 0 (data)     kept streams numbered q = 0, 1, .. in user order, in the order the solver leaves them; symbol j of
+ *                       stream q: byte q n_symbols + j
+ *   stream 1 (noise)    receive antenna a = k nr + i, symbol j: CN sample a n_symbols + j, scaled by sqrt(noise_var)
+ *   At K = 3, Nr = Nt = 2, Ns = 1 these are exactly the positions of mcle_run_ia.  Channel and start are drawn in f64 for
+ *   either dtype (the solver is f64 only); the walk draws in the call's dtype.
+ * Outputs, each NULL or: d_sym_err / d_bit_err [count] (0xFFFFFFFF: flagged by the solver -- mcle_ia_solve_general's d_skipped
+ *   -- counted in n_skipped and nowhere else, its stream slots 0); d_stream_sym_err / d_stream_bit_err [count][4][6] by slot
+ *   (user, kept stream), 0 on an inactive slot; d_ns [count][4] streams kept per user; d_sinr [count][4][6] linear, 0 on an
+ *   inactive slot; d_capacity, d_iterations [count]; d_bigH [count][K nr][K nt] and d_F_init / d_F / d_U [count][4][D][D]
+ *   complex128 in the solver's padded layout (d_F_init all zero when no start is drawn).
+ *   d_counters: n_symbols / n_bits are the figures with every CONFIGURED stream active (n_symbols sum_k ns[k] per realization,
+ *   the mcle_run_comp convention); a realization sent n_symbols sum_k d_ns[.][k].
+ * The per-realization arrays do not depend on the slice, the grid or how [first, first + count) is split.  Scratch for the
+ * channels, starts, solutions and link records of one slice stays <= 1 GiB.
+ * mcle_ctx_last_kernel: "ia_general_link f64|f32 D<4|6> pairs|single" (pairs: n_symbols even, two columns per lane). */
+int mcle_run_ia_general(mcle_ctx* ctx, int dtype, const mcle_ia_general_cfg* cfg, int n_symbols, int demod_method,
+                        uint64_t seed, uint64_t first, uint64_t count, mcle_counters* d_counters, uint32_t* d_sym_err,
+                        uint32_t* d_bit_err, uint32_t* d_stream_sym_err, uint32_t* d_stream_bit_err, int32_t* d_ns,
+                        double* d_sinr, double* d_capacity, uint32_t* d_iterations, void* d_bigH, void* d_F_init, void* d_F,
+                        void* d_U);
+
 /* ---- block diagonalisation of a multi-user downlink (SURVEY 8(f).3 tail) --------------------
  * comm/waterfilling.py:15-92 doWF: d_gains [batch][n] channel POWER gains -> optimum powers
  * d_powers [batch][n] (same order) and the water level d_mu [batch] (may be NULL); n <= 64. */

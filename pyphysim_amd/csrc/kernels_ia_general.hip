@@ -15,6 +15,7 @@
 // iteration earlier or later than the reference's, so iteration counts are equal when the test is not what ends the
 // loop (tests/golden/f3c_ia_general.npz pins both regimes).
 #include "common.hpp"
+#include "ia_general.hpp"
 
 namespace mcle {
 #define MCLE_IAG_NS iag
@@ -29,23 +30,16 @@ namespace mcle {
 #undef MCLE_IAG_D
 }  // namespace mcle
 
-using namespace mcle;
+namespace mcle {
 
-extern "C" {
-
-int mcle_ia_solve_general(mcle_ctx* ctx, const mcle_ia_general_cfg* cfg, const void* d_bigH, const void* d_F_init,
-                          void* d_F, void* d_U, double* d_sinr, double* d_capacity, uint32_t* d_iterations,
-                          int32_t* d_ns, uint32_t* d_skipped, double* d_every_capacity, size_t batch) {
-    if (ctx) ctx->last_kernel[0] = 0;
-    MCLE_REQUIRE(ctx != nullptr && cfg != nullptr && d_bigH != nullptr && d_F != nullptr && d_U != nullptr, "null argument");
+int ia_general_check(const mcle_ia_general_cfg* cfg, bool have_start) {
     MCLE_REQUIRE(cfg->K >= 2 && cfg->K <= iag::KM, "K must be in [2, %d]", iag::KM);
     MCLE_REQUIRE(cfg->nr >= 1 && cfg->nr <= iag6::D && cfg->nt >= 1 && cfg->nt <= iag6::D,
                  "Nr and Nt must be in [1, %d]", iag6::D);
-    const bool big = cfg->nr > iag::D || cfg->nt > iag::D;       // matrices (and the padded array layout) of 6 x 6 instead of 4 x 4
     MCLE_REQUIRE(cfg->solver >= 1 && cfg->solver <= 3, "solver must be alt_min (1), min_leakage (2) or max_sinr (3)");
     MCLE_REQUIRE(cfg->initialize_with == 0 || cfg->initialize_with == 3, "initialize_with must be 'fix' (0) or 'svd' (3)");
     MCLE_REQUIRE(cfg->initialize_with != 3 || cfg->nr == cfg->nt, "the 'svd' start is defined for Nr == Nt");
-    MCLE_REQUIRE(cfg->initialize_with != 0 || d_F_init != nullptr || cfg->stream_selection == 2,
+    MCLE_REQUIRE(cfg->initialize_with != 0 || have_start || cfg->stream_selection == 2,
                  "The precoder must be manually set, since you specified the 'fix' initialize_with option.");
     MCLE_REQUIRE(cfg->stream_selection >= 0 && cfg->stream_selection <= 2, "stream_selection must be 0, 1 or 2");
     MCLE_REQUIRE(cfg->stream_selection != 2 || cfg->nr == cfg->nt, "brute-force selection starts from 'svd' (Nr == Nt)");
@@ -59,29 +53,11 @@ int mcle_ia_solve_general(mcle_ctx* ctx, const mcle_ia_general_cfg* cfg, const v
         const int lim = cfg->nr < cfg->nt ? cfg->nr : cfg->nt;
         MCLE_REQUIRE(cfg->ns[k] >= 1 && cfg->ns[k] <= lim, "Ns[%d] = %d must be in [1, min(Nr, Nt) = %d]", k, cfg->ns[k], lim);
     }
-    if (batch == 0) return MCLE_OK;
-    int rc = ctx->bind();
-    if (rc) return rc;
-    if (big) {
-        iag6::Params pp;
-        pp.K = cfg->K;
-        pp.nr = cfg->nr;
-        pp.nt = cfg->nt;
-        for (int k = 0; k < iag6::KM; ++k) pp.ns[k] = k < cfg->K ? cfg->ns[k] : 0;
-        pp.solver = cfg->solver;
-        pp.init = cfg->initialize_with;
-        pp.max_iter = cfg->max_iterations;
-        pp.select = cfg->stream_selection;
-        pp.nv = cfg->noise_var;
-        pp.rel = cfg->relative_factor;
-        ctx->set_kernel("ia_general<6> K=%d %dx%d", pp.K, pp.nr, pp.nt);
-        hipLaunchKernelGGL(iag6::k_ia_general, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, ctx->stream, pp,
-                           (const double2*)d_bigH, (const double2*)d_F_init, (double2*)d_F, (double2*)d_U, d_sinr,
-                           d_capacity, d_iterations, d_ns, d_skipped, d_every_capacity, batch);
-        MCLE_LAUNCH_CHECK();
-        return MCLE_OK;
-    }
-    iag::Params pp;
+    return MCLE_OK;
+}
+
+template <typename P> static P ia_general_params(const mcle_ia_general_cfg* cfg) {
+    P pp;
     pp.K = cfg->K;
     pp.nr = cfg->nr;
     pp.nt = cfg->nt;
@@ -92,12 +68,48 @@ int mcle_ia_solve_general(mcle_ctx* ctx, const mcle_ia_general_cfg* cfg, const v
     pp.select = cfg->stream_selection;
     pp.nv = cfg->noise_var;
     pp.rel = cfg->relative_factor;
+    return pp;
+}
+
+int ia_general_launch(mcle_ctx* ctx, const mcle_ia_general_cfg* cfg, const void* d_bigH, const void* d_F_init, void* d_F,
+                      void* d_U, double* d_sinr, double* d_capacity, uint32_t* d_iterations, int32_t* d_ns,
+                      uint32_t* d_skipped, double* d_every_capacity, size_t batch) {
+    // matrices (and the padded array layout) of 6 x 6 instead of 4 x 4
+    if (ia_general_capacity(cfg) == iag6::D) {
+        const iag6::Params pp = ia_general_params<iag6::Params>(cfg);
+        ctx->set_kernel("ia_general<6> K=%d %dx%d", pp.K, pp.nr, pp.nt);
+        hipLaunchKernelGGL(iag6::k_ia_general, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, ctx->stream, pp,
+                           (const double2*)d_bigH, (const double2*)d_F_init, (double2*)d_F, (double2*)d_U, d_sinr,
+                           d_capacity, d_iterations, d_ns, d_skipped, d_every_capacity, batch);
+        MCLE_LAUNCH_CHECK();
+        return MCLE_OK;
+    }
+    const iag::Params pp = ia_general_params<iag::Params>(cfg);
     ctx->set_kernel("ia_general<4> K=%d %dx%d", pp.K, pp.nr, pp.nt);
     hipLaunchKernelGGL(iag::k_ia_general, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, ctx->stream, pp,
                        (const double2*)d_bigH, (const double2*)d_F_init, (double2*)d_F, (double2*)d_U, d_sinr,
                        d_capacity, d_iterations, d_ns, d_skipped, d_every_capacity, batch);
     MCLE_LAUNCH_CHECK();
     return MCLE_OK;
+}
+
+}  // namespace mcle
+
+using namespace mcle;
+
+extern "C" {
+
+int mcle_ia_solve_general(mcle_ctx* ctx, const mcle_ia_general_cfg* cfg, const void* d_bigH, const void* d_F_init,
+                          void* d_F, void* d_U, double* d_sinr, double* d_capacity, uint32_t* d_iterations,
+                          int32_t* d_ns, uint32_t* d_skipped, double* d_every_capacity, size_t batch) {
+    if (ctx) ctx->last_kernel[0] = 0;
+    MCLE_REQUIRE(ctx != nullptr && cfg != nullptr && d_bigH != nullptr && d_F != nullptr && d_U != nullptr, "null argument");
+    int rc = ia_general_check(cfg, d_F_init != nullptr);
+    if (rc) return rc;
+    if (batch == 0) return MCLE_OK;
+    if ((rc = ctx->bind())) return rc;
+    return ia_general_launch(ctx, cfg, d_bigH, d_F_init, d_F, d_U, d_sinr, d_capacity, d_iterations, d_ns, d_skipped,
+                             d_every_capacity, batch);
 }
 
 }  // extern "C"

@@ -1066,6 +1066,80 @@ class Engine:
             out["every_capacity"] = every.get()[:, :int(np.prod(ns_list))]     # one value per stream combination
         return out
 
+    def run_ia_general(self, K, nr, nt, Ns, n_symbols, noise_var, seed, first, count, solver="max_sinr", select=None,
+                       initialize_with="random", max_iterations=60, relative_factor=1e-6, method=DEMOD_MINDIST, dtype=None,
+                       per_realization=False, outputs=()):
+        """The IA link on a general geometry, fused (csrc/pipeline_ia_general.hip, include/mcle.h at mcle_run_ia_general;
+        apps/ia/simulate_ia.py with Nr, Nt, Ns as parameters, apps/ia/simulate_greedy_ia.py): K <= 4 users of nr x nt <= 6 x 6
+        antennas, Ns = configured streams per user (int or one per user), solver 'alt_min' / 'min_leakage' / 'max_sinr' from a
+        'random' start drawn on the device or the 'svd' start, select None / 'greedy' / 'brute' (brute force always starts
+        from 'svd'); n_symbols per KEPT stream at unit power per user.
+        -> the counter dict ('n_symbols' / 'n_bits': the figures with every configured stream active) with 'sum_capacity'
+        (+ '_sq') and 'ia_runned_iterations' (+ '_sq') summed over the valid realizations, as run_ia; with
+        per_realization=True (counters, dict(sym_err [count], bit_err [count], stream_sym_err / stream_bit_err [count, K, 6]
+        by (user, kept stream), ns [count, K], capacity [count], iterations [count])).  `outputs` names what else to copy
+        back into that dict: 'big_H' [count, K nr, K nt], 'F_init' / 'F' / 'U' [count, K, D, D] (the solver's padded layout,
+        D = 4 while max(nr, nt) <= 4, else 6), 'sinr' [count, K, 6].  Outside the envelope -> ValueError, last_kernel() == '';
+        else 'ia_general_link f64|f32 D<4|6> pairs|single'."""
+        known = ("big_H", "F_init", "F", "U", "sinr")
+        for name in outputs:
+            if name not in known:
+                raise ValueError("unknown output %r (known: %s)" % (name, ", ".join(known)))
+        if outputs and not per_realization:
+            raise ValueError("outputs come with per_realization=True")
+        if solver not in ("alt_min", "min_leakage", "max_sinr"):
+            raise ValueError("the general-geometry solvers are 'alt_min', 'min_leakage' and 'max_sinr' (got %r)" % (solver,))
+        if initialize_with not in ("random", "svd"):
+            raise ValueError("initialize_with must be 'random' or 'svd'")
+        K, nr, nt, count = int(K), int(nr), int(nt), int(count)
+        ns_list = [int(Ns)] * K if np.isscalar(Ns) else [int(n) for n in Ns]
+        if len(ns_list) != K:
+            raise ValueError("Ns must be an int or one value per user")
+        cfg = _lib.IaGeneralCfg()
+        cfg.K, cfg.nr, cfg.nt = K, nr, nt
+        for k in range(4):
+            cfg.ns[k] = ns_list[k] if k < K else 0
+        cfg.solver = _lib.IA_SOLVERS[solver]
+        cfg.initialize_with = 3 if (initialize_with == "svd" or select == "brute") else 0
+        cfg.max_iterations = int(max_iterations)
+        cfg.stream_selection = _lib.IA_STREAM_SELECTION[select]
+        cfg.noise_var, cfg.relative_factor = float(noise_var), float(relative_factor)
+        dt = self._dt(dtype)
+        D = 4 if max(nr, nt) <= 4 else 6
+        in_envelope = 2 <= K <= 4 and 1 <= nr <= 6 and 1 <= nt <= 6     # anything else is refused by the library below
+        cnt = self.new_counters()
+        se, be = self.empty(count, np.uint32), self.empty(count, np.uint32)
+        ns, cap, its = self.empty((count, 4), np.int32), self.empty(count, np.float64), self.empty(count, np.uint32)
+        opt = {}
+        if per_realization:
+            opt["stream_sym_err"] = self.empty((count, 4, 6), np.uint32)
+            opt["stream_bit_err"] = self.empty((count, 4, 6), np.uint32)
+            shapes = dict(big_H=(count, K * nr, K * nt), F_init=(count, 4, D, D), F=(count, 4, D, D), U=(count, 4, D, D))
+            for name in outputs:
+                if name == "sinr":
+                    opt[name] = self.empty((count, 4, 6), np.float64)
+                else:
+                    opt[name] = self.empty(shapes[name] if in_envelope else (0,), np.complex128)
+        ptr = lambda name: opt[name].ptr if name in opt else None
+        self._raise_value(self.lib.mcle_run_ia_general(
+            self.ctx, dt, byref(cfg), int(n_symbols), int(method), int(seed), int(first), count, cnt.ptr, se.ptr, be.ptr,
+            ptr("stream_sym_err"), ptr("stream_bit_err"), ns.ptr, ptr("sinr"), cap.ptr, its.ptr, ptr("big_H"), ptr("F_init"),
+            ptr("F"), ptr("U")))
+        res = self._counters(cnt)
+        sev, caps, iters = se.get(), cap.get(), its.get().astype(np.int64)
+        valid = sev != 0xFFFFFFFF
+        res["sum_capacity"] = float(caps[valid].sum())
+        res["sum_capacity_sq"] = float(np.square(caps[valid]).sum())
+        res["ia_runned_iterations"] = int(iters[valid].sum())
+        res["ia_runned_iterations_sq"] = int(np.square(iters[valid]).sum())
+        if not per_realization:
+            return res
+        out = dict(sym_err=sev, bit_err=be.get(), ns=ns.get()[:, :K], capacity=caps, iterations=iters)
+        for name, arr in opt.items():
+            host = arr.get()
+            out[name] = host if name == "big_H" else host[:, :K]
+        return res, out
+
     def ia_closed_form(self, big_H, noise_var):
         """big_H [batch, 6, 6] complex128 -> dict(F [batch,3,2], U [batch,3,2], sinr [batch,3],
         capacity [batch], skipped [batch])."""

@@ -75,6 +75,18 @@ class Result:
         return res
 
     @staticmethod
+    def from_histogram(name, histogram):
+        """CHOICETYPE state after histogram[c] updates with choice c, for every c (len(histogram) choices)."""
+        hist = np.asarray(histogram)
+        if hist.ndim != 1 or hist.size == 0 or np.any(hist < 0) or np.any(hist != np.round(hist)):
+            raise ValueError("a histogram is a non-empty 1-D array of non-negative counts")
+        res = Result(name, Result.CHOICETYPE, choice_num=int(hist.size))
+        res._value += np.round(hist).astype(int)
+        res._total = int(res._value.sum())
+        res.num_updates = res._total
+        return res
+
+    @staticmethod
     def from_counters(name, update_type, err_sum, err_sq_sum, units_per_update, num_updates):
         """From exact integer sums of per-realization error counts e_r: SUM -> value = sum e_r;
         RATIO(e_r, units) -> value/total plus sum and sum of squares of e_r/units."""

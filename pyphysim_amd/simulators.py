@@ -691,3 +691,119 @@ class CompSimulator(BatchedSimulationRunner):
             res.add_result(Result.from_batch("sinr_%s" % v, Result.RATIOTYPE, g("sinr_%s_sum" % v), float(ns),
                                              g("sinr_%s_sum" % v), g("sinr_%s_sq" % v), ns))
         return res
+
+
+class GeneralIaSimulator(BatchedSimulationRunner):
+    """The IA link on any geometry the general solver covers (the reference's apps/ia/simulate_ia.py with Nr, Nt, Ns as
+    parameters -- apps/ia/IA_Results_NrxNt(Ns).py runs K = 3, Nr = 5, Nt = 3, Ns = 2 -- and apps/ia/simulate_greedy_ia.py,
+    3 x 3 with Ns = 3 under a stream-selection wrapper): `K` <= 4 users of `Nr` x `Nt` <= 6 x 6 antennas, `Ns` configured
+    streams per user (a scalar or one value per user), `solver` 'alt_min' / 'min_leakage' / 'max_sinr' from a 'random' or
+    'svd' start, `stream_selection` None / 'greedy' (GreedStreamIASolver) / 'brute' (BruteForceStreamIASolver, always from
+    'svd').  One Engine.run_ia_general per batch: channel and start drawn on the device, the solver of
+    Engine.ia_solve_general, NSymbs symbols per KEPT stream.  'SNR' is unpacked.
+
+    Results, formed per realization with that realization's own totals as the two apps form them: 'symbol_errors',
+    'num_symbols', 'bit_errors', 'num_bits' (SUM); 'ber', 'ser' (RATIO against the bits / symbols actually sent);
+    'sum_capacity', 'ia_runned_iterations' (RATIO against 1); with a stream selection 'stream_statistics' (CHOICE: index
+    ravel_multi_index(Ns_final - 1, Ns_configured) of prod(Ns_configured) choices, simulate_greedy_ia.py:417-426).  A
+    realization the solver flags is left out of every Result.  Sums travel through EXTRA_KEYS (the histogram as one key per
+    choice), so sharding and resume keep them.
+
+    Not covered: the closed-form and MMSE solvers, which exist on the 3-user 2 x 2 one-stream geometry only (IaSimulator);
+    the apps' 'ia_cost' Result; a transmit power other than 1 and path loss -- the greedy app's 'NoPathLoss' scenario is this
+    link in the normalisation of simulate_ia.py: P = 1, noise_var = 1 / SNR."""
+
+    SOLVERS = ("alt_min", "min_leakage", "max_sinr")
+    _SUMS = ("sent_symbols", "sent_symbols_sq", "ber_sum", "ber_sq", "ser_sum", "ser_sq", "sum_capacity", "sum_capacity_sq",
+             "ia_runned_iterations", "ia_runned_iterations_sq")
+    EXTRA_INT_KEYS = ("sent_symbols", "sent_symbols_sq", "ia_runned_iterations", "ia_runned_iterations_sq")
+
+    def __init__(self, SNR, K=3, Nr=3, Nt=3, Ns=2, solver="max_sinr", stream_selection=None, initialize_with="random",
+                 max_iterations=60, relative_factor=1e-6, modulator="qam", M=16, NSymbs=200, rep_max=1000, seed=0,
+                 batch_size=4096, dtype="f64", demod="auto", engine=None, common_random_numbers=False, process_group=None):
+        super().__init__(batch_size=batch_size, process_group=process_group)
+        if solver not in self.SOLVERS:
+            raise ValueError("the general-geometry solvers are 'alt_min', 'min_leakage' and 'max_sinr' (got %r); the closed "
+                             "form and MMSE exist for K = 3, 2 x 2, Ns = 1 only: IaSimulator" % (solver,))
+        if stream_selection not in (None, "greedy", "brute"):
+            raise ValueError("stream_selection must be None, 'greedy' or 'brute'")
+        if initialize_with not in ("random", "svd"):
+            raise ValueError("initialize_with must be 'random' or 'svd'")
+        K = int(K)
+        ns = [int(Ns)] * K if np.isscalar(Ns) else [int(n) for n in Ns]
+        if len(ns) != K or min(ns, default=0) < 1:
+            raise ValueError("Ns must be a positive int or one per user")
+        self.rep_max = rep_max
+        self.seed = int(seed)
+        self.dtype = dtype
+        self.common_random_numbers = common_random_numbers
+        self._engine = engine
+        self.modulator = make_modulator(modulator, M, engine) if isinstance(modulator, str) else modulator
+        if demod == "auto":
+            demod = "slicer" if isinstance(self.modulator, QAM) else "mindist"
+        self.demod_method = _lib.DEMOD_QAM_SLICER if demod == "slicer" else _lib.DEMOD_MINDIST
+        self.Ns = tuple(ns)
+        self.stream_selection = stream_selection
+        self.relative_factor = float(relative_factor)
+        self.num_choices = int(np.prod(ns)) if stream_selection else 0
+        self.EXTRA_KEYS = self._SUMS + tuple("streams_c%d" % c for c in range(self.num_choices))
+        self.EXTRA_INT_KEYS = GeneralIaSimulator.EXTRA_INT_KEYS + self.EXTRA_KEYS[len(self._SUMS):]
+        self.params.add("SNR", np.atleast_1d(np.asarray(SNR, dtype=float)))
+        self.params.set_unpack_parameter("SNR")
+        for k, v in (("modulator", self.modulator.name), ("K", K), ("Nr", int(Nr)), ("Nt", int(Nt)),
+                     ("Ns", "x".join(str(n) for n in ns)), ("NSymbs", int(NSymbs)), ("solver", solver),
+                     ("stream_selection", str(stream_selection)), ("initialize_with", initialize_with),
+                     ("max_iterations", int(max_iterations))):
+            self.params.add(k, v)
+
+    engine = _LinkSimulator.engine
+    _seed_for = _LinkSimulator._seed_for
+    _bind = _LinkSimulator._bind
+    _noise_var = staticmethod(_LinkSimulator._noise_var)
+
+    def _run_batch(self, current_parameters, first_rep, count):
+        p = current_parameters
+        eng = self._bind()
+        res, a = eng.run_ia_general(p["K"], p["Nr"], p["Nt"], self.Ns, p["NSymbs"], self._noise_var(p), self._seed_for(p),
+                                    first_rep, count, solver=p["solver"], select=self.stream_selection,
+                                    initialize_with=p["initialize_with"], max_iterations=p["max_iterations"],
+                                    relative_factor=self.relative_factor, method=self.demod_method, dtype=self.dtype,
+                                    per_realization=True)
+        c = dict(res)
+        ok = a["sym_err"] != 0xFFFFFFFF
+        ns = a["ns"][ok].astype(np.int64)
+        sent = int(p["NSymbs"]) * ns.sum(axis=1)                       # symbols the realization actually sent
+        Kb = int(self.modulator.K)
+        ser = a["sym_err"][ok].astype(np.float64) / sent
+        ber = a["bit_err"][ok].astype(np.float64) / (sent * Kb)
+        c["sent_symbols"], c["sent_symbols_sq"] = int(sent.sum()), int(np.square(sent).sum())
+        c["ser_sum"], c["ser_sq"] = float(ser.sum()), float(np.square(ser).sum())
+        c["ber_sum"], c["ber_sq"] = float(ber.sum()), float(np.square(ber).sum())
+        if self.num_choices:
+            index = np.ravel_multi_index(tuple((ns - 1).T), self.Ns) if ns.size else np.zeros(0, dtype=np.int64)
+            hist = np.bincount(index, minlength=self.num_choices)
+            for ch in range(self.num_choices):
+                c["streams_c%d" % ch] = int(hist[ch])
+        return c
+
+    def _results_from_counters(self, current_parameters, c):
+        from .simulations import Result, SimulationResults
+        res = SimulationResults()
+        n = int(c["n_realizations"])
+        Kb = int(self.modulator.K)
+        gi = lambda k: int(round(c.get(k, 0)))
+        gf = lambda k: float(c.get(k, 0.0))
+        sent, sent_sq = gi("sent_symbols"), gi("sent_symbols_sq")
+        res.add_result(Result.from_counters("symbol_errors", Result.SUMTYPE, c["sym_errors"], c["sym_errors_sq"], 1, n))
+        res.add_result(Result.from_batch("num_symbols", Result.SUMTYPE, sent, 0, float(sent), float(sent_sq), n))
+        res.add_result(Result.from_counters("bit_errors", Result.SUMTYPE, c["bit_errors"], c["bit_errors_sq"], 1, n))
+        res.add_result(Result.from_batch("num_bits", Result.SUMTYPE, sent * Kb, 0, float(sent * Kb), float(sent_sq * Kb * Kb), n))
+        res.add_result(Result.from_batch("ber", Result.RATIOTYPE, int(c["bit_errors"]), sent * Kb, gf("ber_sum"), gf("ber_sq"), n))
+        res.add_result(Result.from_batch("ser", Result.RATIOTYPE, int(c["sym_errors"]), sent, gf("ser_sum"), gf("ser_sq"), n))
+        cap, cap_sq = gf("sum_capacity"), gf("sum_capacity_sq")
+        res.add_result(Result.from_batch("sum_capacity", Result.RATIOTYPE, cap, n, cap, cap_sq, n))
+        its, its_sq = gi("ia_runned_iterations"), gi("ia_runned_iterations_sq")
+        res.add_result(Result.from_batch("ia_runned_iterations", Result.RATIOTYPE, its, n, float(its), float(its_sq), n))
+        if self.num_choices:
+            res.add_result(Result.from_histogram("stream_statistics", [gi("streams_c%d" % ch) for ch in range(self.num_choices)]))
+        return res
