@@ -145,53 +145,43 @@ enum {
                                       family -- like no_mfma, the option selects a kernel and does not shrink the envelope.  (2048, 4x4)
                                       in complex128 is refused with it: the generic kernel needs 168 KiB of LDS there.  f32_mfma = 1
                                       comes first at complex64 (1024, 4x4). */
-    MCLE_OPT_F64_THREADS = 8,      /* complex128 config-4 kernel at (1024, 4x4): 0 = the quarter-wave kernel (round 6,
-                                      csrc/pipeline_mimo_qw.hip: a wavefront owns one time class n mod 4 of all antennas, samples in
-                                      registers between radix-16 passes, three workgroups per CU, the channel contraction on
-                                      v_mfma_f64_4x4x4) wherever its envelope holds -- full band, even cyclic prefix, decisions by
-                                      slicer or certificate -- and the planar radix-16 form elsewhere (default); 260 = the same,
-                                      explicit; 262 = quarter-wave bounded for two wavefronts per SIMD; 261 = the planar radix-16
-                                      form (one transform per wavefront, the channel fused with the span-1 butterflies: the default
-                                      of rounds 4-5); 257 = that with a separate channel stage; 258 = 261 with every layer-1 twiddle
-                                      from the table;
-                                      512 = radix-4 stages, two antennas per thread, 512 threads; 256 = radix-4 stages, four antennas
-                                      per thread, 256 threads (all of them: same results contract; A/B times in DESIGN.md 5.5 / 5.10).
-                                      complex64 (the planar family on planes of floats): 0 = radix-16 passes with a SEPARATE channel
-                                      stage at a four-wavefront register bound (default); 257 = the same at a three-wavefront
-                                      bound; 259 = the fused channel stage; 512 / 256 as above.
-                                      fft_size 2048 with four receive antennas and Nt >= 3: 512 = four antennas per thread (512 threads,
-                                      nothing spilled; the default where it is the faster form), 1024 = two antennas per thread.
-                                      complex128 at (256, 4x4) and (512, 4x4), same envelope: 0 / 260 = the full-wave kernel (256:
-                                      csrc/pipeline_mimo_fw.hip, one realization per wavefront) / the half-wave kernel (512:
-                                      csrc/pipeline_mimo_pw.hip, two wavefronts per realization), both with channel AND decode on
-                                      v_mfma_f64_4x4x4; 262 = bounded for two wavefronts per SIMD; 261 = the planar radix-4 form of
-                                      rounds 3-5 (in fact any value but 0 / 260 / 262; at 512 and 2048 any but 0 / 260 / 262 / 265 - 268); both
-                                      arithmetics at 256 (complex64: 0 = two wavefronts per SIMD, 262 = three); (256, 2x2): the full-wave
-                                      kernel with two realizations per wavefront, and with 261 or outside the envelope the GENERIC
-                                      kernel -- the planar family has no (256, 2x2) kernel, the generic one is faster there;
-                                      (2048, 4x4): the eighth-wave kernel (512 threads, one register bound: 262 = 0).  (1024, 4x4): since the end of round 6 the DEFAULT (0) is the
-                                      quarter-wave decomposition with the decode on the matrix cores as well (pipeline_mimo_pw.hip,
-                                      NW = 4; 263 = the same, explicit; 264 = two wavefronts per SIMD); 260 / 262 select the first
-                                      quarter-wave kernel (pipeline_mimo_qw.hip, VALU decode).
-                                      Since round 7 the part-wave kernel (512, 1024 and 2048 points) adds the signal AFTER the
-                                      receive transform -- the channel is flat, so only the noise is transformed and H X joins it
-                                      on v_mfma_f64_4x4x4 in front of the decode; 265 = its time-domain form of round 6 (transmit
-                                      transform, channel on the samples) at all three sizes, same counts: the A/B partner.
-                                      Since round 10 its (antenna, time class) partial transforms are dealt by LANE ROW -- both
-                                      samples of a Philox noise block in one wavefront, their words exchanged in registers, one
-                                      workgroup barrier fewer; 266 = the map of rounds 6 - 9 (a wavefront owns one time class of
-                                      all antennas, the words go through LDS) at all three sizes, same counts, tag suffix "/a".
-                                      Since round 20 the wavefronts of a realization exchange their partial spectra as complex values
-                                      in two halves, each lane refilling the LDS slots it has just read -- one workgroup barrier
-                                      fewer; 267 = ownership by lane row with the exchange by re / im planes of
-                                      rounds 10 - 19 (barrier B3) at all three sizes, same counts, tag suffix "/x": the witness.
-                                      The default takes the exchange in complex halves at 1024 and 2048 points and keeps the planes
-                                      at 512, where the halves were not faster in every run; 268 = the exchange in complex halves
-                                      at all three sizes, same counts, tag suffix "/h".
-                                      (1024, Nt < 4, Nr = 4), either arithmetic: 0 = the radix-16 form, any other value the radix-4 one.
-                                      mcle_ctx_last_kernel names the kernel that served the call -- for the part-wave kernel the size
-                                      and the form, "mimo_ofdm_pw<NW>/freq" or ".../time" (+ "/w2" at the two-wavefront bound, + "/a" for 266, "/x" for 267, "/h" for 268); the
-                                      whole grammar is listed there. */
+    MCLE_OPT_F64_THREADS = 8,      /* which of the kept config-4 kernels serves mcle_run_mimo_ofdm (A/B runs, kernel-vs-kernel tests: same
+                                      results contract).  Read off csrc/c4_select.hpp (c4_select: the one place that reads the value; a
+                                      name per value there); why each form exists and what it measured: DESIGN.md 5.5 - 5.28.  The wave
+                                      kernels (fw / pw / qw) need their envelope -- full band, even cyclic prefix, decisions by the
+                                      slicer or a certificate (qw: no on-axis certificate) -- and OUTSIDE it every value that names one
+                                      selects what 261 selects.  "P" = the planar family's kernel of the shape, tag
+                                      "mimo_ofdm_planar<N,NT,NR> f64|f32 ah<AH> w<WPS> v<VAR>" (ah, w, v below); pw<NW> = tag
+                                      "mimo_ofdm_pw<NW>/freq", fw<NA> = "mimo_ofdm_fw<NA> f64|f32 w<WPS>", qw = "mimo_ofdm_qw w<WPS>".
+
+                                      value | (256, 2x2 / 4x4)     | c128 (512, 4x4) | c128 (1024, 4x4)  | c64 (1024, 4x4) | c128 (2048, 4x4)
+                                      ------+----------------------+-----------------+-------------------+-----------------+-----------------
+                                          0 | fw w3 (c64: w2)      | pw<2>           | pw<4>             | P ah4 w4 v4     | pw<8>
+                                        256 | as 261               | as 261          | P ah4 w2 v0       | P ah4 w2 v0     | as 261
+                                        257 | as 261               | as 261          | P ah4 w2 v4       | P ah4 w3 v4     | as 261
+                                        258 | as 261               | as 261          | P ah4 w2 v28      | as 0            | as 261
+                                        259 | as 261               | as 261          | as 261            | P ah4 w4 v12    | as 261
+                                        260 | as 0                 | as 0            | qw w3             | as 0            | as 0
+                                        261 | 4x4: P ah2 w3 v0,    | P ah2 w3 v0     | P ah4 w2 v12      | as 0            | P ah4 w2 v0
+                                            | 2x2: generic kernel  |                 |                   |                 |
+                                        262 | fw w2 (c64: w3)      | pw<2> + "/w2"   | qw w2             | as 0            | as 0 (one bound)
+                                        263 | as 261               | as 261          | as 0              | as 0            | as 261
+                                        264 | as 261               | as 261          | pw<4> + "/w2"     | as 0            | as 261
+                                        265 | as 261               | "mimo_ofdm_pw<NW>/time": the time-domain form      | as 0 | (as 512, 1024)
+                                        266 | as 261               | pw<NW> + "/a": a wavefront owns a time class        | as 0 | (as 512, 1024)
+                                        267 | as 261               | pw<NW> + "/x": lane rows, exchange by re / im planes | as 0 | (as 512, 1024)
+                                        268 | as 261               | pw<NW> + "/h": lane rows, exchange in complex halves | as 0 | (as 512, 1024)
+                                        512 | as 261               | as 261          | P ah2 w4 v0       | P ah2 w4 v0     | as 261
+                                       1024 | as 261               | as 261          | as 261            | as 0            | P ah2 w4 v0
+
+                                      What the default (0) of the part-wave kernel is: lane rows, the exchange in complex halves at 1024 and
+                                      2048 points and by re / im planes at 512 -- 267 / 268 name an exchange and carry the suffix also
+                                      where it is the default's.  complex64 at (512, 4x4) and (2048, 4x4): P at every value (2048: ah4 w2 v0,
+                                      and ah2 w4 v0 for 1024).  Other geometries, either arithmetic: (1024, Nt < 4, Nr = 4): 0 = radix-16
+                                      passes (complex128 ah4 w2 v12, complex64 ah4 w4 v4), any other value the radix-4 form ah2 w4 v0;
+                                      (2048, Nt < 4, Nr = 4): 512 = ah4 w2 v0 (the default in complex64), 1024 = ah2 w4 v0 (the default
+                                      in complex128); every other shape has one kernel and ignores the value.  f64_generic, no_mfma and
+                                      f32_mfma come first (see there). */
     MCLE_OPT_BD_RUNTIME_SOLVE = 9, /* 1: the block-diagonalisation pipeline solves with the run-time-sized routine (private
                                       arrays in scratch) also where the compile-time-sized one (K nr <= 6) applies */
     MCLE_OPT_DEMOD_NOCERT = 10,    /* 1: min-distance decisions of a square Gray QAM always through the table search (candidate

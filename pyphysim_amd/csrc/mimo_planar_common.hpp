@@ -51,6 +51,18 @@ __global__ __launch_bounds__(64) void k_mimo_filters_planar(MimoParams pp, uint6
     rec[2 * NT * NR] = mk<T>(ok ? (T)0 : (T)1, (T)0);
 }
 
+// host: launch_sliced (pipe_common.hpp) with this record and its kernel -- the planar, full-wave, quarter-wave and part-wave launchers
+template <typename T, int N, int NT, int NR, typename Link>
+inline int launch_sliced_planar(mcle_ctx* ctx, const MimoParams& pp, uint64_t seed, uint64_t first, uint64_t count, uint64_t k_slice,
+                                uint32_t* d_sym, uint32_t* d_bit, Link&& link) {
+    return launch_sliced(ctx, first, count, k_slice, d64_rec<NT, NR>() * sizeof(cx<T>), d_sym, d_bit,
+                         [&](void* recs, uint64_t at, uint64_t n) {
+                             hipLaunchKernelGGL((k_mimo_filters_planar<T, N, NT, NR>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0,
+                                                ctx->stream, pp, seed, at, n, (cx<T>*)recs);
+                         },
+                         link);
+}
+
 // lanes l and l ^ 32 exchange: (a of the lower half, b of the upper half) stay, the other two cross over --
 // x = {lower: own a, upper: the partner's b}, y = {lower: the partner's a, upper: own b}  (v_permlane32_swap_b32)
 __device__ __forceinline__ void swap32_pair(double a, double b, double& x, double& y) {

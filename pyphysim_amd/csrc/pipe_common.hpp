@@ -2,6 +2,7 @@
 #pragma once
 #include "common.hpp"
 #include "modem.hpp"
+#include "c4_select.hpp"
 
 namespace mcle {
 
@@ -60,6 +61,29 @@ inline uint64_t flush_min_units(uint64_t base, uint64_t k_samples, uint64_t samp
     const uint64_t m = k_samples / (samples > 0 ? samples : 1);
     return m > base ? m : base;
 }
+
+// A launch in slices of at most k_slice realizations, so that the record buffer (rec_bytes per realization, the context's scratch)
+// stays bounded: per slice records(recs, first, n) starts the kernel that writes the slice's records and link(recs, first, n, sym, bit)
+// the kernel that walks them; sym / bit: the per-realization outputs at the slice (or null).
+template <typename Records, typename Link>
+inline int launch_sliced(mcle_ctx* ctx, uint64_t first, uint64_t count, uint64_t k_slice, size_t rec_bytes, uint32_t* d_sym,
+                         uint32_t* d_bit, Records&& records, Link&& link) {
+    const uint64_t slice = count < k_slice ? count : k_slice;
+    void* recs = nullptr;
+    int rc;
+    if ((rc = ctx->scratch((size_t)slice * rec_bytes, &recs))) return rc;
+    for (uint64_t off = 0; off < count; off += slice) {
+        const uint64_t n = count - off < slice ? count - off : slice;
+        records(recs, first + off, n);
+        MCLE_LAUNCH_CHECK();
+        link(recs, first + off, n, d_sym ? d_sym + off : nullptr, d_bit ? d_bit + off : nullptr);
+        MCLE_LAUNCH_CHECK();
+    }
+    return MCLE_OK;
+}
+
+// names the kernel a config-4 launcher is about to start (mcle_ctx_last_kernel)
+inline void set_c4_kernel(mcle_ctx* ctx, const C4Plan& plan) { c4_plan_tag(plan, ctx->last_kernel, (int)sizeof(ctx->last_kernel)); }
 
 template <typename T> ModemParams<T> pipe_modem(const mcle_ctx* ctx, int method) {
     ModemParams<T> p;

@@ -366,15 +366,15 @@ __global__ __launch_bounds__(256, WPS) void k_run_mimo_ofdm_fw(MimoParams pp, Mo
 }
 
 template <typename T, int NA, int WPS, int ABL = 0>
-static int launch_mimo_ofdm_fw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
-                               mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit) {
+static int launch_mimo_ofdm_fw(mcle_ctx* ctx, const C4Plan& plan, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first,
+                               uint64_t count, mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit) {
     constexpr int N = 256, NT = NA, NR = NA, kRec = d64_rec<NT, NR>(), RZ = 4 / NA;
     int rc;
     void* tw = nullptr;
     if ((rc = ctx->get_twiddles(N, sizeof(T) == 8 ? MCLE_F64 : MCLE_F32, &tw))) return rc;
     MimoParams pp{cfg->cp_size, cfg->num_used, cfg->n_ofdm_sym, cfg->mmse, cfg->noise_var};
     ModemParams<T> mp = pipe_modem<T>(ctx, cfg->demod_method);
-    const int dec = walk_dec_kind(ctx, mp);
+    const int dec = walk_dec_kind(ctx, mp);          // (the plan's form; here for the on-axis constants it leaves in mp)
     mp.grid.G = 0;
     const size_t tab_len = ((size_t)mp.M + 1) & ~(size_t)1;
     const size_t lds = (size_t)4 * fw_plane_bytes<T>() + (2 * tab_len + 4 * RZ * (kRec + 1)) * sizeof(cx<T>) +
@@ -387,62 +387,37 @@ static int launch_mimo_ofdm_fw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uin
         case WDEC_AXIS4_CERT: kern = k_run_mimo_ofdm_fw<T, NA, WDEC_AXIS4_CERT, WPS, ABL>; break;
         default: break;
     }
-    ctx->set_kernel("mimo_ofdm_fw<%d> %s w%d", NA, sizeof(T) == 8 ? "f64" : "f32", WPS);
+    set_c4_kernel(ctx, plan);
     MCLE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int per_cu = (int)((size_t)160 * 1024 / (lds + 512));
     if (per_cu < 1) per_cu = 1;
     if (per_cu > WPS) per_cu = WPS;                            // 256 threads = one wavefront per SIMD and workgroup
     const uint64_t resident = (uint64_t)ctx->n_cu * per_cu;
     const uint64_t kSlice = 1ull << 20;
-    const uint64_t slice = count < kSlice ? count : kSlice;
-    void* recs = nullptr;
-    if ((rc = ctx->scratch((size_t)slice * kRec * sizeof(cx<T>), &recs))) return rc;
-    for (uint64_t off = 0; off < count; off += slice) {
-        const uint64_t n = count - off < slice ? count - off : slice;
-        hipLaunchKernelGGL((k_mimo_filters_planar<T, N, NT, NR>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, pp, seed,
-                           first + off, n, (cx<T>*)recs);
-        MCLE_LAUNCH_CHECK();
+    return launch_sliced_planar<T, N, NT, NR>(ctx, pp, seed, first, count, kSlice, d_sym, d_bit,
+                                              [&](void* recs, uint64_t at, uint64_t n, uint32_t* sym, uint32_t* bit) {
         const unsigned grid = (unsigned)oversubscribed_grid(ctx, resident, (n + 4 * RZ - 1) / (4 * RZ), 8, 16);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, ctx->stream, pp, mp, seed, first + off, n, (const cx<T>*)tw,
-                           (const cx<T>*)recs, d_counters, d_sym ? d_sym + off : nullptr, d_bit ? d_bit + off : nullptr);
-        MCLE_LAUNCH_CHECK();
-    }
-    return MCLE_OK;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, ctx->stream, pp, mp, seed, at, n, (const cx<T>*)tw, (const cx<T>*)recs,
+                           d_counters, sym, bit);
+    });
 }
 
-// 0 = launched; MCLE_E_UNSUPPORTED = outside the envelope (the caller stays on the planar kernel)
-int run_mimo_ofdm_fw(mcle_ctx* ctx, int dtype, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
-                     mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit) {
-    if (!(cfg->fft_size == 256 && cfg->nt == cfg->nr && (cfg->nt == 4 || cfg->nt == 2) && cfg->num_used == 256 && (cfg->cp_size & 1) == 0))
-        return MCLE_E_UNSUPPORTED;
-    if (ctx->M > 256) return MCLE_E_UNSUPPORTED;
-    {
-        ModemParams<double> mp = pipe_modem<double>(ctx, cfg->demod_method);
-        if (walk_dec_kind(ctx, mp) == WDEC_GENERIC) return MCLE_E_UNSUPPORTED;     // no certificate: the planar kernel's candidate grid
-    }
-    const bool two = ctx->opt[MCLE_OPT_F64_THREADS] == 262;
-    if (dtype == MCLE_F32) {
-        // complex64: registers bounded for TWO wavefronts per SIMD (nothing spilled): 1.46e8 realizations/s at 4 x 4 and 3.25e8 at 2 x 2 against
-        // 1.30 / 2.69e8 at three (34 - 62 spilled registers) and 1.05 / 2.33e8 at four; the planar kernel: 1.29 / 1.67e8.  262: three.
-        if (cfg->nt == 2)
-            return two ? launch_mimo_ofdm_fw<float, 2, 3>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit)
-                       : launch_mimo_ofdm_fw<float, 2, 2>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-        return two ? launch_mimo_ofdm_fw<float, 4, 3>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit)
-                   : launch_mimo_ofdm_fw<float, 4, 2>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-    }
+// The full-wave instantiations <arithmetic, NA, wavefronts per SIMD, ablation>: 2 x 2 and 4 x 4 in both arithmetics at either bound
+// (which is the default per arithmetic: c4_select.hpp)
+int launch_mimo_ofdm_fw(mcle_ctx* ctx, const C4Plan& p, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
+                        mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit) {
+#define MCLE_FW(T_, NA_, WPS_, ABL_)                                                                                     \
+    if (p.f64 == (sizeof(T_) == 8) && p.nt == NA_ && p.wps == WPS_ && p.abl == ABL_)                                     \
+        return launch_mimo_ofdm_fw<T_, NA_, WPS_, ABL_>(ctx, p, cfg, seed, first, count, d_counters, d_sym, d_bit);
+    MCLE_FW(float, 2, 2, 0) MCLE_FW(float, 2, 3, 0) MCLE_FW(float, 4, 2, 0) MCLE_FW(float, 4, 3, 0)
+    MCLE_FW(double, 2, 2, 0) MCLE_FW(double, 2, 3, 0) MCLE_FW(double, 4, 2, 0) MCLE_FW(double, 4, 3, 0)
 #ifdef MCLE_EXPERIMENTS
-    switch ((int)ctx->opt[MCLE_OPT_F64_VARIANT]) {
-#define MCLE_FW_ABL(V_) case V_: if (cfg->nt == 4) return launch_mimo_ofdm_fw<double, 4, 3, V_>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit); break;
-        MCLE_FW_ABL(32) MCLE_FW_ABL(64) MCLE_FW_ABL(128) MCLE_FW_ABL(256) MCLE_FW_ABL(512) MCLE_FW_ABL(1024) MCLE_FW_ABL(2016)
+#define MCLE_FW_ABL(V_) MCLE_FW(double, 4, 3, V_)
+    MCLE_FW_ABL(32) MCLE_FW_ABL(64) MCLE_FW_ABL(128) MCLE_FW_ABL(256) MCLE_FW_ABL(512) MCLE_FW_ABL(1024) MCLE_FW_ABL(2016)
 #undef MCLE_FW_ABL
-        default: break;
-    }
 #endif
-    if (cfg->nt == 2)
-        return two ? launch_mimo_ofdm_fw<double, 2, 2>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit)
-                   : launch_mimo_ofdm_fw<double, 2, 3>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-    return two ? launch_mimo_ofdm_fw<double, 4, 2>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit)
-               : launch_mimo_ofdm_fw<double, 4, 3>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
+#undef MCLE_FW
+    MCLE_REQUIRE(false, "internal: no full-wave MIMO-OFDM kernel <%d> %s w%d ablation %d", p.nt, p.f64 ? "f64" : "f32", p.wps, p.abl);
 }
 
 }  // namespace mcle

@@ -488,11 +488,11 @@ __global__ __launch_bounds__(kPipeBlock, WAVES) void k_run_mimo_ofdm_mfma(MimoPa
     }
 }
 
-// host side: 0 = launched, MCLE_E_UNSUPPORTED = outside this kernel's envelope (caller uses k_run_mimo_ofdm)
-int run_mimo_ofdm_mfma(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
-                       mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit) {
-    if (cfg->fft_size != kF16N || cfg->nt != 4 || cfg->nr != 4) return MCLE_E_UNSUPPORTED;
-    if (ctx->opt[MCLE_OPT_NO_MFMA]) return MCLE_E_UNSUPPORTED;
+// host side: complex64 (1024, 4 x 4), on request (c4_select.hpp)
+int launch_mimo_ofdm_mfma(mcle_ctx* ctx, const C4Plan& plan, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
+                          mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit) {
+    MCLE_REQUIRE(!plan.f64 && plan.n == kF16N && plan.nt == 4 && plan.nr == 4, "internal: no matrix-core MIMO-OFDM kernel <%d,%d,%d>",
+                 plan.n, plan.nt, plan.nr);
     int rc;
     void* tw = nullptr;
     if ((rc = ctx->get_twiddles(kF16N, MCLE_F32, &tw))) return rc;
@@ -505,32 +505,26 @@ int run_mimo_ofdm_mfma(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uint64_t se
     // middle stage, operand loads of the four antennas first, pass twiddles fetched per pass (default: 7 spilled
     // registers, 1.535-1.544 ms per 65 536 realizations); 32 = the same with the twiddles resident (28 spilled, 1.555);
     // 30 = antenna-by-antenna passes; 21 = 2 waves per SIMD (229 VGPRs, no spills) with the noise under P1 / P2 (1.62)
-    const int variant = ctx->opt[MCLE_OPT_MFMA_VARIANT] ? (int)ctx->opt[MCLE_OPT_MFMA_VARIANT] : 36;
+    const int variant = plan.variant;
     const int waves = variant / 10 == 2 ? 2 : 3;
     auto kern = variant == 30 ? k_run_mimo_ofdm_mfma<3, 0> : variant == 21 ? k_run_mimo_ofdm_mfma<2, 1>
                 : variant == 32 ? k_run_mimo_ofdm_mfma<3, 2> : k_run_mimo_ofdm_mfma<3, 6>;
-    ctx->set_kernel("mimo_ofdm_mfma v%d", variant);
+    set_c4_kernel(ctx, plan);
     MCLE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int per_cu = (int)((size_t)160 * 1024 / (lds + 512));
     if (per_cu < 1) per_cu = 1;
     if (per_cu > waves) per_cu = waves;     // __launch_bounds__(256, WAVES)
     const uint64_t resident = (uint64_t)ctx->n_cu * per_cu;
     const uint64_t kSlice = 1ull << 18;          // realizations per filter + link pair: bounds the record buffer (69 MB)
-    const uint64_t slice = count < kSlice ? count : kSlice;
-    void* recs = nullptr;
-    if ((rc = ctx->scratch((size_t)slice * kMimoRec * sizeof(float2), &recs))) return rc;
-    for (uint64_t off = 0; off < count; off += slice) {
-        const uint64_t n = count - off < slice ? count - off : slice;
-        hipLaunchKernelGGL(k_mimo_filters, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, pp, seed, first + off, n,
-                           (float2*)recs);
-        MCLE_LAUNCH_CHECK();
-        const unsigned grid = (unsigned)oversubscribed_grid(ctx, resident, n);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kPipeBlock), lds, ctx->stream, pp, mp, seed, first + off, n,
-                           (const float2*)tw, (const float2*)recs, d_counters, d_sym ? d_sym + off : nullptr,
-                           d_bit ? d_bit + off : nullptr);
-        MCLE_LAUNCH_CHECK();
-    }
-    return MCLE_OK;
+    return launch_sliced(ctx, first, count, kSlice, kMimoRec * sizeof(float2), d_sym, d_bit,
+                         [&](void* recs, uint64_t at, uint64_t n) {
+                             hipLaunchKernelGGL(k_mimo_filters, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, pp, seed, at, n, (float2*)recs);
+                         },
+                         [&](void* recs, uint64_t at, uint64_t n, uint32_t* sym, uint32_t* bit) {
+                             const unsigned grid = (unsigned)oversubscribed_grid(ctx, resident, n);
+                             hipLaunchKernelGGL(kern, dim3(grid), dim3(kPipeBlock), lds, ctx->stream, pp, mp, seed, at, n, (const float2*)tw,
+                                                (const float2*)recs, d_counters, sym, bit);
+                         });
 }
 
 }  // namespace mcle

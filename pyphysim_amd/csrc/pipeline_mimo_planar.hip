@@ -22,7 +22,7 @@
 //     certificate, of anything else through the candidate grid (both decision-identical to the sweep; the complex128
 //     certificate by construction up to 2^11 level spacings and by a <= 1e-14-per-symbol bound beyond, modem.hpp / mcle.h).
 // Round 4: a FAMILY, not a benchmark point -- fft_size in {256, 512, 1024, 2048} (a trailing radix-2 stage for 512 / 2048,
-// like fft.hpp), Nt <= Nr in {2, 4} square plus the Nr > Nt shapes listed in run_mimo_ofdm_planar; the reference's OFDM /
+// like fft.hpp), Nt <= Nr in {2, 4} square plus the Nr > Nt shapes listed in launch_mimo_ofdm_planar_t; the reference's OFDM /
 // Blast take any of them (modulators/ofdm.py:52-94, mimo/mimo.py:264-309, :609-660).
 // No matrix cores here, on purpose: v_mfma_f64_16x16x4_f64 issues in 65 cycles (2048 flops: 31.5 flop/clk/SIMD, measured,
 // scripts/experiments/f64_rates.hip) against 4.8 cycles for a v_fma_f64 (26.7 flop/clk), does NOT overlap with VALU work
@@ -473,8 +473,8 @@ __global__ __launch_bounds__((N / 4) * (NR / AH), WPS) void k_run_mimo_ofdm_plan
 
 // one geometry: filters + link, sliced so that the record buffer stays bounded
 template <typename T, int N, int NT, int NR, int AH, int WPS, int VAR = 0>
-static int launch_mimo_ofdm_planar(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
-                                mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit) {
+static int launch_mimo_ofdm_planar(mcle_ctx* ctx, const C4Plan& plan, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first,
+                                   uint64_t count, mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit) {
     constexpr int kRec = d64_rec<NT, NR>(), TB = (N / 4) * (NR / AH);
     int rc;
     void* tw = nullptr;
@@ -489,7 +489,7 @@ static int launch_mimo_ofdm_planar(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg,
     MCLE_REQUIRE(lds + 512 <= (size_t)160 * 1024, "planar MIMO-OFDM kernel: %zu B of LDS do not fit (fft_size %d, %d receive antennas)",
                  lds, N, NR);
     auto kern = k_run_mimo_ofdm_planar<T, N, NT, NR, AH, WPS, VAR>;
-    ctx->set_kernel("mimo_ofdm_planar<%d,%d,%d> %s ah%d w%d v%d", N, NT, NR, sizeof(T) == 8 ? "f64" : "f32", AH, WPS, VAR);
+    set_c4_kernel(ctx, plan);
     MCLE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int per_cu = (int)((size_t)160 * 1024 / (lds + 512));
     const int by_waves = (WPS * 256) / TB > 0 ? (WPS * 256) / TB : 1;          // what __launch_bounds__ allocated registers for
@@ -497,207 +497,61 @@ static int launch_mimo_ofdm_planar(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg,
     if (per_cu > by_waves) per_cu = by_waves;
     const uint64_t resident = (uint64_t)ctx->n_cu * per_cu;
     const uint64_t kSlice = 1ull << 18;     // realizations per filter + link pair: bounds the record buffer (138 MB)
-    const uint64_t slice = count < kSlice ? count : kSlice;
-    void* recs = nullptr;
-    if ((rc = ctx->scratch((size_t)slice * kRec * sizeof(cx<T>), &recs))) return rc;
-    for (uint64_t off = 0; off < count; off += slice) {
-        const uint64_t n = count - off < slice ? count - off : slice;
-        hipLaunchKernelGGL((k_mimo_filters_planar<T, N, NT, NR>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, pp, seed,
-                           first + off, n, (cx<T>*)recs);
-        MCLE_LAUNCH_CHECK();
+    return launch_sliced_planar<T, N, NT, NR>(ctx, pp, seed, first, count, kSlice, d_sym, d_bit,
+                                              [&](void* recs, uint64_t at, uint64_t n, uint32_t* sym, uint32_t* bit) {
         // (realizations per workgroup: >= 8, and enough for the counters' flush to disappear at the small shapes -- pipe_common.hpp)
         const unsigned grid = (unsigned)oversubscribed_grid(ctx, resident, n, flush_min_units(8, sizeof(T) == 4 ? 25600 : 12800, (uint64_t)N * NR), 16);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(TB), lds, ctx->stream, pp, mp, seed, first + off, n,
-                           (const cx<T>*)tw, (const cx<T>*)recs, d_counters, d_sym ? d_sym + off : nullptr,
-                           d_bit ? d_bit + off : nullptr);
-        MCLE_LAUNCH_CHECK();
-    }
-    return MCLE_OK;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(TB), lds, ctx->stream, pp, mp, seed, at, n, (const cx<T>*)tw, (const cx<T>*)recs,
+                           d_counters, sym, bit);
+    });
 }
 
-// host side: 0 = launched, MCLE_E_UNSUPPORTED = outside this family's envelope (caller uses k_run_mimo_ofdm<double, ...>).
-// Geometry table: (fft_size, Nt x Nr) -> antennas per thread AH, threads, workgroups per CU (LDS), wavefronts per SIMD:
-//   1024  4x4   radix-16 form: 4 antennas / wave-per-antenna, 256 threads, 2 workgroups per CU, 2 wavefronts per SIMD
-//  (1024  4x4   2   512   2   4  radix-4, option f64_threads=512)   2048  4x4   2  1024   1   4        512  4x4   2   256   3   3        256  4x4   2  128  5  3
-//   1024  2x2   2   256   3   3        2048  2x2   2   512   2   4        512  2x2   2   128   5   3        256  2x2   2   64  8  2
-// Nt < Nr (mimo/mimo.py:264-309 takes any): every 1 <= Nt <= Nr <= 4 with Nr >= 2 at every size runs the Nr geometry (Nr = 3: three
-// antennas per thread, one group); antenna groups past Nt idle in the IFFT.
-// complex64 (round 4): the same kernels on planes of floats.  Half the LDS per workgroup, 80 - 140 registers per thread where
-// complex128 takes 120 - 250: the radix-4 geometries keep the complex128 table's wavefronts-per-SIMD bound (doubling it spilled
-// 10 - 77 registers in every 4-receive-antenna shape), the radix-16 form of the benchmark size runs four workgroups per CU
-// instead of two.
-// (last day of round 6: at 256 points, and at 512 with two receive antennas, that bound was the complex128 LDS limit carried over --
-//  those complex64 kernels hold 78 - 93 registers and a quarter of the planes, and ran at 0.47 - 0.69 of their issue slots
-//  (profiles/r06/c4_pmc.log): two more wavefronts per SIMD there, +5 ... +18 %.  NOT elsewhere: 512 points with three receive antennas
-//  LOSE 14 - 37 % at four wavefronts per SIMD, 1024 / 2048 do not move -- profiles/r06/planar_f32_wps_ab.log)
-#ifndef MCLE_PLANAR_F32_WPS_PLUS
-#define MCLE_PLANAR_F32_WPS_PLUS 2
-#endif
-template <typename T> constexpr int planar_wps(int n, int nt, int nr, int w64) {
-    if (sizeof(T) == 4 && w64 <= 3 && ((n == 256 && !(nt == 4 && nr == 4)) || (n == 512 && nr == 2))) return w64 + MCLE_PLANAR_F32_WPS_PLUS;
-#ifndef MCLE_PLANAR_F64_256_WPS3
-#define MCLE_PLANAR_F64_256_WPS3 0
-#endif
-    if (MCLE_PLANAR_F64_256_WPS3 && sizeof(T) == 8 && n == 256 && nr <= 3 && w64 == 2) return 3;   // (A/B on the last day: +1.5 ... -1.5 %, not adopted)
-    return w64;
-}
-
-// pipeline_mimo_qw.hip: the quarter-wave kernel of the benchmark geometry (complex128; MCLE_E_UNSUPPORTED outside its envelope)
-int run_mimo_ofdm_qw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
-                     mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit);
-
-// pipeline_mimo_fw.hip: one realization per wavefront at fft_size 256 (complex128, 4 x 4; MCLE_E_UNSUPPORTED outside its envelope)
-int run_mimo_ofdm_fw(mcle_ctx* ctx, int dtype, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
-                     mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit);
-
-// pipeline_mimo_pw.hip: 1 / NW of the time samples per wavefront at fft_size 512 (NW = 2) and 1024 (NW = 4), decode on the matrix cores
-int run_mimo_ofdm_pw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
-                     mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit);
-
+// The planar family's instantiations; which of them serves a call: c4_select.hpp (c4_select_planar).  The radix-4 table has every
+// 1 <= Nt <= Nr <= 4 with Nr >= 2 at 256 .. 2048 but (256, 2 x 2), antennas per thread and wavefronts per SIMD from planar_r4_ah /
+// planar_r4_wps; the rows with numbers are the forms an option or a default names beside it.
 template <typename T>
-static int run_mimo_ofdm_planar_t(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
-                                  mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit) {
+static int launch_mimo_ofdm_planar_t(mcle_ctx* ctx, const C4Plan& p, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first,
+                                     uint64_t count, mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit) {
     constexpr bool F64 = sizeof(T) == 8;
-    const int n = cfg->fft_size, nt = cfg->nt, nr = cfg->nr;
-#define MCLE_F64_GEOM(N_, NT_, NR_, AH_, WPS_)                                                                      \
-    if (n == N_ && nt == NT_ && nr == NR_)                                                                          \
-        return launch_mimo_ofdm_planar<T, N_, NT_, NR_, AH_, planar_wps<T>(N_, NT_, NR_, WPS_)>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-    // (1024, 4 x 4), the benchmark geometry: radix-16 passes, one transform per wavefront, 256 threads (default since round 4:
-    // 10.66 ms per 262 144 realizations against 11.65 for the 512-thread radix-4 form and 12.15 for the 256-thread one,
-    // profiles/r04/c4_f64_r16_ab.log).  MCLE_OPT_F64_THREADS: 512 = radix-4, two antennas per thread; 256 = radix-4, four
-    // antennas per thread, twiddles in registers.  MCLE_OPT_F64_VARIANT 1 .. 3: timing bounds on the 512-thread form.
-    if (n == 256 && nt == 4 && nr == 4) {    // ((256, 2 x 2) never comes here: mcle_run_mimo_ofdm tries the full-wave kernel itself, then the generic one)
-        {   // (either arithmetic since the last day of round 6: complex64 contracts on the VALU, pipeline_mimo_fw.hip)
-            // round 6: the FULL-WAVE kernel (pipeline_mimo_fw.hip: a realization is one wavefront -- the quarter-wave kernel's register
-            // passes without its radix-4 exchange stage, channel AND decode on v_mfma_f64_4x4x4, no workgroup barrier).
-            // MCLE_OPT_F64_THREADS = 261 (any value but 0 / 260 / 262): the planar radix-4 form of rounds 3-5; 262: full-wave at the
-            // other wavefront bound (complex128 two per SIMD instead of three, complex64 three instead of two).
-            const long long thr = ctx->opt[MCLE_OPT_F64_THREADS];
-            if (thr == 0 || thr == 260 || thr == 262) {
-                const int rq = run_mimo_ofdm_fw(ctx, F64 ? MCLE_F64 : MCLE_F32, cfg, seed, first, count, d_counters, d_sym, d_bit);
-                if (rq != MCLE_E_UNSUPPORTED) return rq;
-            }
-        }
-    }
-    if ((n == 512 || n == 2048) && nt == 4 && nr == 4) {
-        if constexpr (F64) {
-            // round 6: the HALF-WAVE / EIGHTH-WAVE kernel (pipeline_mimo_pw.hip, NW = 2 / 8).  MCLE_OPT_F64_THREADS = 261 (and, at 2048,
-            // 512 / 1024): the planar radix-4 forms; 265: the part-wave kernel in its time-domain form; 266: its default form with
-            // the ownership map of rounds 6 - 9; 267: ownership by lane row with the exchange by re / im planes of rounds 10 - 19 (the default at 512); 268: the exchange in complex halves (the default at 2048).
-            const long long thr = ctx->opt[MCLE_OPT_F64_THREADS];
-            if (thr == 0 || thr == 260 || thr == 262 || thr == 265 || thr == 266 || thr == 267 || thr == 268) {
-                const int rq = run_mimo_ofdm_pw(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-                if (rq != MCLE_E_UNSUPPORTED) return rq;
-            }
-        }
-    }
-    if (n == 1024 && nt == 4 && nr == 4) {
-        if constexpr (F64) {
-            {   // The default since the end of round 6: the quarter-wave decomposition with the DECODE on the matrix cores as well
-                // (pipeline_mimo_pw.hip, NW = 4: 32.4 against 35.2 ms per 2^20 realizations for pipeline_mimo_qw.hip on the same box,
-                // profiles/r06/pw_ab.log).  MCLE_OPT_F64_THREADS = 263: the same, explicit; 264: registers bounded for two wavefronts
-                // per SIMD; 260 / 262: the quarter-wave kernel of pipeline_mimo_qw.hip (VALU decode, four bins per thread).
-                // Since round 7 it adds the signal AFTER the receive transform (no transmit transform: DESIGN.md 5.14); 265: its
-                // time-domain form of round 6; 266: the default form with the ownership map of rounds 6 - 9;
-                // 267: ownership by lane row with the exchange by re / im planes of rounds 10 - 19; 268: the exchange in complex halves, explicit.
-                const long long thr = ctx->opt[MCLE_OPT_F64_THREADS];
-                if (thr == 0 || thr == 263 || thr == 264 || thr == 265 || thr == 266 || thr == 267 || thr == 268) {
-                    const int rq = run_mimo_ofdm_pw(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-                    if (rq != MCLE_E_UNSUPPORTED) return rq;
-                }
-            }
-            // The default since round 6: the QUARTER-WAVE kernel (pipeline_mimo_qw.hip: samples in registers between the passes, three
-            // workgroups per CU, the channel contraction on v_mfma_f64_4x4x4) -- 8.82 against 10.49 ms per 262 144 realizations
-            // (profiles/r06/qw_ab.log).  Outside its envelope (partial band, odd prefix, a constellation without a certificate)
-            // the launch stays on the planar forms below.  MCLE_OPT_F64_THREADS: 260 = quarter-wave (the default, explicit),
-            // 262 = the same bounded for two wavefronts per SIMD, 261 = the planar radix-16 form that was the default until round 5.
-            {
-                const long long thr = ctx->opt[MCLE_OPT_F64_THREADS];
-                if (thr == 0 || thr == 260 || thr == 262) {          // (0: outside the part-wave kernel's envelope nothing reaches this line)
-                    const int rq = run_mimo_ofdm_qw(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-                    if (rq != MCLE_E_UNSUPPORTED) return rq;
-                }
-            }
-#ifdef MCLE_EXPERIMENTS     // the timing-bound variants give WRONG counters by construction: never in the product build
-            switch ((int)ctx->opt[MCLE_OPT_F64_VARIANT]) {
-                case 1: return launch_mimo_ofdm_planar<T, 1024, 4, 4, 2, 4, 1>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-                case 2: return launch_mimo_ofdm_planar<T, 1024, 4, 4, 2, 4, 2>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-                case 3: return launch_mimo_ofdm_planar<T, 1024, 4, 4, 2, 4, 3>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-                default: break;
-            }
-            // section ablation of the headline form (f64_variant = 32 | 64 | ... | 1024, any combination of single sections listed)
-            switch ((int)ctx->opt[MCLE_OPT_F64_VARIANT]) {
-#define MCLE_ABL(V_) case V_: return launch_mimo_ofdm_planar<T, 1024, 4, 4, 4, 2, 12 | V_>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-                MCLE_ABL(32) MCLE_ABL(64) MCLE_ABL(128) MCLE_ABL(256) MCLE_ABL(512) MCLE_ABL(1024) MCLE_ABL(2016) MCLE_ABL(1920) MCLE_ABL(384)
+#define MCLE_PLANAR(N_, NT_, NR_, AH_, WPS_, VAR_)                                                                        \
+    if (p.n == N_ && p.nt == NT_ && p.nr == NR_ && p.ah == (AH_) && p.wps == (WPS_) && p.variant == (VAR_))                     \
+        return launch_mimo_ofdm_planar<T, N_, NT_, NR_, AH_, WPS_, VAR_>(ctx, p, cfg, seed, first, count, d_counters, d_sym, d_bit);
+#define MCLE_PLANAR_R4(N_, NT_, NR_) MCLE_PLANAR(N_, NT_, NR_, planar_r4_ah(NR_), planar_r4_wps(F64, N_, NT_, NR_), 0)
+#define MCLE_PLANAR_R4_SIZE(N_)                                                                                          \
+    MCLE_PLANAR_R4(N_, 1, 2) MCLE_PLANAR_R4(N_, 1, 3) MCLE_PLANAR_R4(N_, 2, 3) MCLE_PLANAR_R4(N_, 3, 3)                  \
+    MCLE_PLANAR_R4(N_, 1, 4) MCLE_PLANAR_R4(N_, 2, 4) MCLE_PLANAR_R4(N_, 3, 4) MCLE_PLANAR_R4(N_, 4, 4)
+    MCLE_PLANAR_R4_SIZE(256)
+    MCLE_PLANAR_R4_SIZE(512) MCLE_PLANAR_R4(512, 2, 2)
+    MCLE_PLANAR_R4_SIZE(1024) MCLE_PLANAR_R4(1024, 2, 2)
+    MCLE_PLANAR_R4_SIZE(2048) MCLE_PLANAR_R4(2048, 2, 2)
+    // radix-4 stages with four antennas per thread: (1024, 4 x 4) and 2048 points with four receive antennas
+    MCLE_PLANAR(1024, 4, 4, 4, 2, 0)
+    MCLE_PLANAR(2048, 1, 4, 4, 2, 0) MCLE_PLANAR(2048, 2, 4, 4, 2, 0) MCLE_PLANAR(2048, 3, 4, 4, 2, 0) MCLE_PLANAR(2048, 4, 4, 4, 2, 0)
+    // radix-16 passes at 1024 points with four receive antennas: variant 4 = separate channel stage, 12 = fused, 28 = fused with every
+    // layer-1 twiddle from the table
+    if constexpr (F64) {
+        MCLE_PLANAR(1024, 1, 4, 4, 2, 12) MCLE_PLANAR(1024, 2, 4, 4, 2, 12) MCLE_PLANAR(1024, 3, 4, 4, 2, 12) MCLE_PLANAR(1024, 4, 4, 4, 2, 12)
+        MCLE_PLANAR(1024, 4, 4, 4, 2, 4) MCLE_PLANAR(1024, 4, 4, 4, 2, 28)
+#ifdef MCLE_EXPERIMENTS     // timing bounds and section ablations: WRONG counters by construction, never in the product build
+        MCLE_PLANAR(1024, 4, 4, 2, 4, 1) MCLE_PLANAR(1024, 4, 4, 2, 4, 2) MCLE_PLANAR(1024, 4, 4, 2, 4, 3)
+#define MCLE_ABL(V_) MCLE_PLANAR(1024, 4, 4, 4, 2, 12 | V_)
+        MCLE_ABL(32) MCLE_ABL(64) MCLE_ABL(128) MCLE_ABL(256) MCLE_ABL(512) MCLE_ABL(1024) MCLE_ABL(2016) MCLE_ABL(1920) MCLE_ABL(384)
 #undef MCLE_ABL
-                default: break;
-            }
 #endif
-            if (ctx->opt[MCLE_OPT_F64_THREADS] == 258)  // every layer-1 twiddle from the table (A/B: 10.95 ms against 10.62 -- the nine
-                return launch_mimo_ofdm_planar<T, 1024, 4, 4, 4, 2, 28>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);   // loads per pass cost more than the eight products)
-        }
-        if (ctx->opt[MCLE_OPT_F64_THREADS] == 256)
-            return launch_mimo_ofdm_planar<T, 1024, 4, 4, 4, 2>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-        if (ctx->opt[MCLE_OPT_F64_THREADS] == 512)
-            return launch_mimo_ofdm_planar<T, 1024, 4, 4, 2, 4>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-        if constexpr (!F64) {
-            // complex64: the SEPARATE channel stage at a four-wavefront register bound is the fast form (4.88 ms per 262 144
-            // realizations; fused 5.08; at a three-wavefront bound 5.26 / 5.47; the matrix-core kernel 5.89 -- min-distance
-            // demodulator, profiles/r04/c4_f32_planar_ab.log); 259 = fused, 257 = the three-wavefront bound (A/B)
-            if (ctx->opt[MCLE_OPT_F64_THREADS] == 259)
-                return launch_mimo_ofdm_planar<T, 1024, 4, 4, 4, 4, 12>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-            if (ctx->opt[MCLE_OPT_F64_THREADS] == 257)
-                return launch_mimo_ofdm_planar<T, 1024, 4, 4, 4, 3, 4>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-            return launch_mimo_ofdm_planar<T, 1024, 4, 4, 4, 4, 4>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-        } else {
-            if (ctx->opt[MCLE_OPT_F64_THREADS] == 257)      // radix-16 passes with the unfused channel stage (A/B)
-                return launch_mimo_ofdm_planar<T, 1024, 4, 4, 4, 2, 4>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-            return launch_mimo_ofdm_planar<T, 1024, 4, 4, 4, 2, 12>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-        }
+    } else {
+        MCLE_PLANAR(1024, 1, 4, 4, 4, 4) MCLE_PLANAR(1024, 2, 4, 4, 4, 4) MCLE_PLANAR(1024, 3, 4, 4, 4, 4) MCLE_PLANAR(1024, 4, 4, 4, 4, 4)
+        MCLE_PLANAR(1024, 4, 4, 4, 4, 12) MCLE_PLANAR(1024, 4, 4, 4, 3, 4)
     }
-    // every Nt <= Nr <= 4 at every size: Nr = 2 / 4 two antennas per thread, Nr = 3 three (one group)
-#define MCLE_F64_SIZE(N_, W2_, W4_)                                                                                  \
-    MCLE_F64_GEOM(N_, 2, 2, 2, W2_) MCLE_F64_SIZE_REST(N_, W2_, W4_)
-#define MCLE_F64_SIZE_REST(N_, W2_, W4_)                                                                             \
-    MCLE_F64_GEOM(N_, 1, 2, 2, W2_)                                                                                  \
-    MCLE_F64_GEOM(N_, 1, 3, 3, 2) MCLE_F64_GEOM(N_, 2, 3, 3, 2) MCLE_F64_GEOM(N_, 3, 3, 3, 2)                        \
-    MCLE_F64_GEOM(N_, 1, 4, 2, W4_) MCLE_F64_GEOM(N_, 2, 4, 2, W4_) MCLE_F64_GEOM(N_, 3, 4, 2, W4_)
-    MCLE_F64_SIZE_REST(256, 2, 3) MCLE_F64_GEOM(256, 4, 4, 2, 3)      // (no (256, 2 x 2): the generic kernel is the faster one, see mcle_run_mimo_ofdm)
-    MCLE_F64_SIZE(512, 3, 3) MCLE_F64_GEOM(512, 4, 4, 2, 3)
-    if (n == 1024 && nr == 4 && ctx->opt[MCLE_OPT_F64_THREADS] == 0) {      // Nt < 4 at the benchmark size: the radix-16 form too
-        constexpr int WR16 = F64 ? 2 : 4, VR16 = F64 ? 12 : 4;       // complex128: fused, 2 workgroups per CU; complex64: unfused, 4
-        if (nt == 1) return launch_mimo_ofdm_planar<T, 1024, 1, 4, 4, WR16, VR16>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-        if (nt == 2) return launch_mimo_ofdm_planar<T, 1024, 2, 4, 4, WR16, VR16>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-        if (nt == 3) return launch_mimo_ofdm_planar<T, 1024, 3, 4, 4, WR16, VR16>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-    }
-    MCLE_F64_SIZE(1024, 3, 4)
-    // 2048 with four receive antennas: 1 024 threads (two antennas per thread) are four wavefronts per SIMD by themselves, i.e. a
-    // 128-register bound that the complex128 form does not meet (36 / 22 spilled registers at 4 x 4 / 3 x 4, complex64 13 / 0).  Four
-    // antennas per thread (512 threads, 256 registers, nothing spilled) is the default where it is the faster form -- 4 x 4 in both
-    // arithmetics (+7 % / +4 %) and 3 x 4 in complex64 (+3 %); 3 x 4 in complex128 keeps the 1 024-thread form WITH its spills (7.38
-    // against 7.70 ms per 65 536 realizations), and so does 2 x 4 in complex128 with 12 (5.75 against 6.74 ms; complex64 2 x 4 and 1 x 4: 2.97 against
-    // 3.71 and 2.79 against 3.51 ms for the 512-thread form): profiles/r05/planar_2048_ab.log.  MCLE_OPT_F64_THREADS: 512 / 1024 force either.
-    if (n == 2048 && nr == 4) {
-        const long long thr = ctx->opt[MCLE_OPT_F64_THREADS];
-        const bool four = thr == 512 || (thr != 1024 && (nt == 4 || !F64));       // complex64: every Nt; complex128: 4 x 4 only
-        if (four) {
-            if (nt == 4) return launch_mimo_ofdm_planar<T, 2048, 4, 4, 4, 2>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-            if (nt == 3) return launch_mimo_ofdm_planar<T, 2048, 3, 4, 4, 2>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-            if (nt == 2) return launch_mimo_ofdm_planar<T, 2048, 2, 4, 4, 2>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-            return launch_mimo_ofdm_planar<T, 2048, 1, 4, 4, 2>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-        }
-    }
-    MCLE_F64_SIZE(2048, 4, 4) MCLE_F64_GEOM(2048, 4, 4, 2, 4)
-#undef MCLE_F64_SIZE
-#undef MCLE_F64_SIZE_REST
-#undef MCLE_F64_GEOM
-    return MCLE_E_UNSUPPORTED;
+#undef MCLE_PLANAR_R4_SIZE
+#undef MCLE_PLANAR_R4
+#undef MCLE_PLANAR
+    MCLE_REQUIRE(false, "internal: no planar MIMO-OFDM kernel <%d,%d,%d> ah%d w%d v%d", p.n, p.nt, p.nr, p.ah, p.wps, p.variant);
 }
 
-int run_mimo_ofdm_planar(mcle_ctx* ctx, int dtype, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
-                         mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit) {
-    return dtype == MCLE_F32 ? run_mimo_ofdm_planar_t<float>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit)
-                             : run_mimo_ofdm_planar_t<double>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
+int launch_mimo_ofdm_planar(mcle_ctx* ctx, const C4Plan& plan, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first,
+                            uint64_t count, mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit) {
+    return plan.f64 ? launch_mimo_ofdm_planar_t<double>(ctx, plan, cfg, seed, first, count, d_counters, d_sym, d_bit)
+                    : launch_mimo_ofdm_planar_t<float>(ctx, plan, cfg, seed, first, count, d_counters, d_sym, d_bit);
 }
 
 }  // namespace mcle

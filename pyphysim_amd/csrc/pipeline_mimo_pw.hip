@@ -809,17 +809,17 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
     }
 }
 
-template <int NW, int WPS, bool TD = false, int ABL = 0, bool ROWS = !TD, bool XCH = ROWS && ABL == 0>
-static int launch_mimo_ofdm_pw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
-                               mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit) {
+template <int NW, int WPS, bool TD, int ABL, bool ROWS, bool XCH>
+static int launch_mimo_ofdm_pw(mcle_ctx* ctx, const C4Plan& plan, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first,
+                               uint64_t count, mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit) {
     using T = double;
-    constexpr int N = 256 * NW, NT = 4, NR = 4, kRec = d64_rec<NT, NR>();
+    constexpr int N = 256 * NW, NT = 4, NR = 4;
     int rc;
     void* tw = nullptr;
     if ((rc = ctx->get_twiddles(N, MCLE_F64, &tw))) return rc;
     MimoParams pp{cfg->cp_size, cfg->num_used, cfg->n_ofdm_sym, cfg->mmse, cfg->noise_var};
     ModemParams<T> mp = pipe_modem<T>(ctx, cfg->demod_method);
-    const int dec = walk_dec_kind(ctx, mp);
+    const int dec = walk_dec_kind(ctx, mp);          // (the plan's form; here for the on-axis constants it leaves in mp)
     mp.grid.G = 0;
     const size_t tab_len = ((size_t)mp.M + 1) & ~(size_t)1;
     const size_t dyn = (size_t)NW * kPwPlane * sizeof(T) + 2 * tab_len * sizeof(cx<T>);      // planes + the two constellation tables
@@ -838,99 +838,45 @@ static int launch_mimo_ofdm_pw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uin
     const int by_waves = WPS * 4 / NW;                         // wavefronts per SIMD x four SIMDs / wavefronts per workgroup
     if (per_cu > by_waves) per_cu = by_waves;
     const uint64_t resident = (uint64_t)ctx->n_cu * per_cu;
-    // which form served the call (mcle_ctx_last_kernel); "/w2": the two-wavefront register bound where three is the default (NW = 2, 4);
-    // "/a": the default form with the ownership map of rounds 6 - 9 (wavefront = class, row = antenna); "/x": ownership by lane row
-    // with the exchange by re / im planes of rounds 10 - 19 (barrier B3) ASKED FOR (267), "/h": the exchange in complex halves asked
-    // for (268) -- what the default picks per size carries no suffix
-    const long long asked = ctx->opt[MCLE_OPT_F64_THREADS];
     static_assert(XCH ? ROWS && ABL == 0 : true, "the exchange in complex halves: default form by lane row only");
-    ctx->set_kernel("mimo_ofdm_pw<%d>/%s%s%s", NW, TD ? "time" : "freq", WPS == (NW == 8 ? 2 : 3) ? "" : "/w2",
-                    !TD && !ROWS ? "/a" : asked == 267 ? "/x" : asked == 268 ? "/h" : "");
+    set_c4_kernel(ctx, plan);
     const uint64_t kSlice = 1ull << 20;          // realizations per record kernel + link kernel pair (553 MB of records; 2^18: three more tails per bench step, -0.6 %)
-    const uint64_t slice = count < kSlice ? count : kSlice;
-    void* recs = nullptr;
-    if ((rc = ctx->scratch((size_t)slice * kRec * sizeof(cx<T>), &recs))) return rc;
-    for (uint64_t off = 0; off < count; off += slice) {
-        const uint64_t n = count - off < slice ? count - off : slice;
-        hipLaunchKernelGGL((k_mimo_filters_planar<T, N, NT, NR>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, pp, seed,
-                           first + off, n, (cx<T>*)recs);
-        MCLE_LAUNCH_CHECK();
+    return launch_sliced_planar<T, N, NT, NR>(ctx, pp, seed, first, count, kSlice, d_sym, d_bit,
+                                              [&](void* recs, uint64_t at, uint64_t n, uint32_t* sym, uint32_t* bit) {
         // (workgroups per resident slot: up to 32 at 1024 points -- 31.36 against 31.53 ms per 2^20 realizations at 16, 31.40 at 48)
         const unsigned grid = (unsigned)oversubscribed_grid(ctx, resident, n, 8, NW == 4 ? 32 : 16);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), dyn, ctx->stream, pp, mp, seed, first + off, n, (const cx<T>*)tw,
-                           (const cx<T>*)recs, d_counters, d_sym ? d_sym + off : nullptr, d_bit ? d_bit + off : nullptr);
-        MCLE_LAUNCH_CHECK();
-    }
-    return MCLE_OK;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), dyn, ctx->stream, pp, mp, seed, at, n, (const cx<T>*)tw, (const cx<T>*)recs,
+                           d_counters, sym, bit);
+    });
 }
 
-// 0 = launched; MCLE_E_UNSUPPORTED = outside the envelope (the caller stays on its other kernels)
-int run_mimo_ofdm_pw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
-                     mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit) {
-    if (!((cfg->fft_size == 512 || cfg->fft_size == 1024 || cfg->fft_size == 2048) && cfg->nt == 4 && cfg->nr == 4 && cfg->num_used == cfg->fft_size &&
-          (cfg->cp_size & 1) == 0))
-        return MCLE_E_UNSUPPORTED;
-    if (ctx->M > 256) return MCLE_E_UNSUPPORTED;
-    {
-        ModemParams<double> mp = pipe_modem<double>(ctx, cfg->demod_method);
-        if (walk_dec_kind(ctx, mp) == WDEC_GENERIC) return MCLE_E_UNSUPPORTED;     // no certificate: the planar kernel's candidate grid
-    }
-    // MCLE_OPT_F64_THREADS: 265 = the time-domain form (three wavefronts per SIMD); 262 / 264 = two wavefronts per SIMD; 266 = the
-    // default form with the ownership map of rounds 6 - 9 (noise words through LDS, barrier B1); 267 = ownership by lane row with the
-    // exchange by re / im planes (barrier B3: the witness of round 20, and what the default still is at 512 points, where the
-    // exchange in complex halves was not faster in every run -- DESIGN.md 5.28); 268 = the exchange in complex halves at all three
-    // sizes (the default at 1024 and 2048); the ablations of the
-    // MCLE_EXPERIMENTS builds (option f64_variant) apply to the time-domain form and to the default form with its default map
-    const bool two = ctx->opt[MCLE_OPT_F64_THREADS] == 262 || ctx->opt[MCLE_OPT_F64_THREADS] == 264;
-    const bool td = ctx->opt[MCLE_OPT_F64_THREADS] == 265;
-    if (ctx->opt[MCLE_OPT_F64_THREADS] == 266) {
-        if (cfg->fft_size == 2048) return launch_mimo_ofdm_pw<8, 2, false, 0, false>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-        if (cfg->fft_size == 512) return launch_mimo_ofdm_pw<2, 3, false, 0, false>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-        return launch_mimo_ofdm_pw<4, 3, false, 0, false>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-    }
-    if (ctx->opt[MCLE_OPT_F64_THREADS] == 268) {
-        if (cfg->fft_size == 2048) return launch_mimo_ofdm_pw<8, 2, false, 0, true, true>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-        if (cfg->fft_size == 512) return launch_mimo_ofdm_pw<2, 3, false, 0, true, true>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-        return launch_mimo_ofdm_pw<4, 3, false, 0, true, true>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-    }
-    if (ctx->opt[MCLE_OPT_F64_THREADS] == 267) {
-        if (cfg->fft_size == 2048) return launch_mimo_ofdm_pw<8, 2, false, 0, true, false>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-        if (cfg->fft_size == 512) return launch_mimo_ofdm_pw<2, 3, false, 0, true, false>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-        return launch_mimo_ofdm_pw<4, 3, false, 0, true, false>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-    }
-    if (cfg->fft_size == 2048) {     // eight wavefronts = 512 threads: one workgroup per CU (86 KiB of LDS), two wavefronts per SIMD
-        return td ? launch_mimo_ofdm_pw<8, 2, true>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit)
-                  : launch_mimo_ofdm_pw<8, 2>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-    }
-#ifdef MCLE_EXPERIMENTS
-#define MCLE_PW_ABL(NW_, V_)                                                                                          \
-    case V_:                                                                                                          \
-        return td ? launch_mimo_ofdm_pw<NW_, 3, true, V_>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit)     \
-                  : launch_mimo_ofdm_pw<NW_, 3, false, V_>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-#define MCLE_PW_ABLS(NW_)                                                                                             \
-    switch ((int)ctx->opt[MCLE_OPT_F64_VARIANT]) {                                                                    \
-        MCLE_PW_ABL(NW_, 32) MCLE_PW_ABL(NW_, 64) MCLE_PW_ABL(NW_, 128) MCLE_PW_ABL(NW_, 256) MCLE_PW_ABL(NW_, 512)   \
-        MCLE_PW_ABL(NW_, 1024) MCLE_PW_ABL(NW_, 2016)                                                                 \
-        default: break;                                                                                               \
-    }
-#else
-#define MCLE_PW_ABLS(NW_)
-#endif
-    if (cfg->fft_size == 512) {
-        MCLE_PW_ABLS(2)
-        if (td) return launch_mimo_ofdm_pw<2, 3, true>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-        // (512 points keep the exchange by re / im planes: profiles/r20/f64_family_rates.json)
-        return two ? launch_mimo_ofdm_pw<2, 2, false, 0, true, false>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit)
-                   : launch_mimo_ofdm_pw<2, 3, false, 0, true, false>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-    }
-    MCLE_PW_ABLS(4)
-#undef MCLE_PW_ABLS
-#ifdef MCLE_EXPERIMENTS
+// The part-wave instantiations <NW, wavefronts per SIMD, time-domain form, ablation, ownership by lane row, exchange in complex
+// halves>; which of them serves a call: c4_select.hpp.  Per size: the map of rounds 6 - 9 (a wavefront owns a time class: noise words
+// through LDS, barrier B1), ownership by lane row with the exchange in complex halves and with the exchange by re / im planes
+// (barrier B3: the witness of round 20 -- DESIGN.md 5.28), the time-domain form; at 512 / 1024 points the default form's exchange
+// bounded for two wavefronts per SIMD as well.
+int launch_mimo_ofdm_pw(mcle_ctx* ctx, const C4Plan& p, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
+                        mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit) {
+#define MCLE_PW(NW_, WPS_, TD_, ABL_, ROWS_, XCH_)                                                                              \
+    if (p.n == 256 * NW_ && p.wps == WPS_ && p.td == TD_ && p.abl == ABL_ && p.rows == ROWS_ && p.halves == XCH_)               \
+        return launch_mimo_ofdm_pw<NW_, WPS_, TD_, ABL_, ROWS_, XCH_>(ctx, p, cfg, seed, first, count, d_counters, d_sym, d_bit);
+#define MCLE_PW_SIZE(NW_, WPS_)                                                                                                 \
+    MCLE_PW(NW_, WPS_, false, 0, false, false) MCLE_PW(NW_, WPS_, false, 0, true, true) MCLE_PW(NW_, WPS_, false, 0, true, false) \
+    MCLE_PW(NW_, WPS_, true, 0, false, false)
+    MCLE_PW_SIZE(2, 3) MCLE_PW(2, 2, false, 0, true, false)
+    MCLE_PW_SIZE(4, 3) MCLE_PW(4, 2, false, 0, true, true)
+    MCLE_PW_SIZE(8, 2)
+#ifdef MCLE_EXPERIMENTS     // section ablations of the time-domain form and of the default form with the exchange by planes
+#define MCLE_PW_ABL(V_)                                                                                                         \
+    MCLE_PW(2, 3, true, V_, false, false) MCLE_PW(2, 3, false, V_, true, false) MCLE_PW(4, 3, true, V_, false, false)           \
+    MCLE_PW(4, 3, false, V_, true, false)
+    MCLE_PW_ABL(32) MCLE_PW_ABL(64) MCLE_PW_ABL(128) MCLE_PW_ABL(256) MCLE_PW_ABL(512) MCLE_PW_ABL(1024) MCLE_PW_ABL(2016)
 #undef MCLE_PW_ABL
 #endif
-    if (td) return launch_mimo_ofdm_pw<4, 3, true>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-    return two ? launch_mimo_ofdm_pw<4, 2>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit)
-               : launch_mimo_ofdm_pw<4, 3>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
+#undef MCLE_PW_SIZE
+#undef MCLE_PW
+    MCLE_REQUIRE(false, "internal: no part-wave MIMO-OFDM kernel <%d> w%d time %d rows %d halves %d ablation %d", p.n / 256, p.wps, (int)p.td,
+                 (int)p.rows, (int)p.halves, p.abl);
 }
 
 }  // namespace mcle

@@ -449,8 +449,8 @@ __global__ __launch_bounds__(256, WPS) void k_run_mimo_ofdm_qw(MimoParams pp, Mo
 }
 
 template <int WPS, int ABL = 0>
-static int launch_mimo_ofdm_qw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
-                               mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit) {
+static int launch_mimo_ofdm_qw(mcle_ctx* ctx, const C4Plan& plan, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first,
+                               uint64_t count, mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit) {
     using T = double;
     constexpr int N = 1024, NT = 4, NR = 4, kRec = d64_rec<NT, NR>();
     int rc;
@@ -464,47 +464,33 @@ static int launch_mimo_ofdm_qw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uin
                        kQwLabBytes + 16;
     MCLE_REQUIRE(lds + 512 <= (size_t)160 * 1024, "quarter-wave MIMO-OFDM kernel: %zu B of LDS do not fit", lds);
     auto kern = k_run_mimo_ofdm_qw<WPS, ABL>;
-    ctx->set_kernel("mimo_ofdm_qw w%d", WPS);
+    set_c4_kernel(ctx, plan);
     MCLE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int per_cu = (int)((size_t)160 * 1024 / (lds + 512));
     if (per_cu < 1) per_cu = 1;
     if (per_cu > WPS) per_cu = WPS;                            // 256 threads = one wavefront per SIMD and workgroup
     const uint64_t resident = (uint64_t)ctx->n_cu * per_cu;
     const uint64_t kSlice = 1ull << 18;
-    const uint64_t slice = count < kSlice ? count : kSlice;
-    void* recs = nullptr;
-    if ((rc = ctx->scratch((size_t)slice * kRec * sizeof(cx<T>), &recs))) return rc;
-    for (uint64_t off = 0; off < count; off += slice) {
-        const uint64_t n = count - off < slice ? count - off : slice;
-        hipLaunchKernelGGL((k_mimo_filters_planar<T, N, NT, NR>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, pp, seed,
-                           first + off, n, (cx<T>*)recs);
-        MCLE_LAUNCH_CHECK();
+    return launch_sliced_planar<T, N, NT, NR>(ctx, pp, seed, first, count, kSlice, d_sym, d_bit,
+                                              [&](void* recs, uint64_t at, uint64_t n, uint32_t* sym, uint32_t* bit) {
         const unsigned grid = (unsigned)oversubscribed_grid(ctx, resident, n, 8, 16);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, ctx->stream, pp, mp, seed, first + off, n, (const cx<T>*)tw,
-                           (const cx<T>*)recs, d_counters, d_sym ? d_sym + off : nullptr, d_bit ? d_bit + off : nullptr);
-        MCLE_LAUNCH_CHECK();
-    }
-    return MCLE_OK;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, ctx->stream, pp, mp, seed, at, n, (const cx<T>*)tw, (const cx<T>*)recs,
+                           d_counters, sym, bit);
+    });
 }
 
-// 0 = launched; MCLE_E_UNSUPPORTED = outside the envelope (the caller stays on the planar kernel)
-int run_mimo_ofdm_qw(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
-                     mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit) {
-    if (!(cfg->fft_size == 1024 && cfg->nt == 4 && cfg->nr == 4 && cfg->num_used == 1024 && (cfg->cp_size & 1) == 0))
-        return MCLE_E_UNSUPPORTED;
-    if (ctx->M > 256) return MCLE_E_UNSUPPORTED;
-    // min-distance decisions through a certificate (square QAM, QPSK) or the slicer: the sweep behind the certificate is the rare path here
-    if (cfg->demod_method != MCLE_DEMOD_QAM_SLICER && modem_cert(ctx, cfg->demod_method) == 0) return MCLE_E_UNSUPPORTED;
+// The quarter-wave instantiations <wavefronts per SIMD, ablation> (min-distance decisions through a certificate -- square QAM, QPSK --
+// or the slicer: the sweep behind the certificate is the rare path here; which calls come here: c4_select.hpp)
+int launch_mimo_ofdm_qw(mcle_ctx* ctx, const C4Plan& p, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
+                        mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit) {
+#define MCLE_QW(WPS_, ABL_) \
+    if (p.wps == WPS_ && p.abl == ABL_) return launch_mimo_ofdm_qw<WPS_, ABL_>(ctx, p, cfg, seed, first, count, d_counters, d_sym, d_bit);
+    MCLE_QW(3, 0) MCLE_QW(2, 0)
 #ifdef MCLE_EXPERIMENTS
-    switch ((int)ctx->opt[MCLE_OPT_F64_VARIANT]) {
-#define MCLE_QW_ABL(V_) case V_: return launch_mimo_ofdm_qw<3, V_>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-        MCLE_QW_ABL(32) MCLE_QW_ABL(64) MCLE_QW_ABL(128) MCLE_QW_ABL(256) MCLE_QW_ABL(512) MCLE_QW_ABL(1024) MCLE_QW_ABL(2016) MCLE_QW_ABL(384)
-#undef MCLE_QW_ABL
-        default: break;
-    }
+    MCLE_QW(3, 32) MCLE_QW(3, 64) MCLE_QW(3, 128) MCLE_QW(3, 256) MCLE_QW(3, 512) MCLE_QW(3, 1024) MCLE_QW(3, 2016) MCLE_QW(3, 384)
 #endif
-    if (ctx->opt[MCLE_OPT_F64_THREADS] == 262) return launch_mimo_ofdm_qw<2>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
-    return launch_mimo_ofdm_qw<3>(ctx, cfg, seed, first, count, d_counters, d_sym, d_bit);
+#undef MCLE_QW
+    MCLE_REQUIRE(false, "internal: no quarter-wave MIMO-OFDM kernel w%d ablation %d", p.wps, p.abl);
 }
 
 }  // namespace mcle

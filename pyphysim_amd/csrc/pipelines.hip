@@ -1019,7 +1019,7 @@ int run_flat_impl(mcle_ctx* ctx, const FlatParams& fp, int method, uint64_t seed
 }
 
 template <typename T, int N, int NA>
-int run_mimo_impl(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
+int run_mimo_impl(mcle_ctx* ctx, const C4Plan& plan, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
                   mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit) {
     int rc;
     void* tw = nullptr;
@@ -1031,7 +1031,7 @@ int run_mimo_impl(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, u
                        (size_t)NA * cfg->num_used;
     MCLE_REQUIRE(lds <= 160 * 1024, "configuration needs %zu bytes of LDS (limit 160 KiB)", lds);
     auto kern = k_run_mimo_ofdm<T, N, NA>;
-    ctx->set_kernel("mimo_ofdm_generic<%d,%d> %s", N, NA, sizeof(T) == 8 ? "f64" : "f32");
+    set_c4_kernel(ctx, plan);
     void* filters = nullptr;
     MCLE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int per_cu = (int)((size_t)160 * 1024 / (lds + 512));  // gfx950: 160 KiB of LDS per CU
@@ -1094,14 +1094,16 @@ int run_tdl_impl(mcle_ctx* ctx, const mcle_ofdm_tdl_cfg* cfg, uint64_t seed, uin
 }  // namespace mcle
 
 namespace mcle {
-// pipeline_mimo_mfma.hip: f32, FFT 1024, 4x4 on the matrix cores; MCLE_E_UNSUPPORTED outside that envelope
-// pipeline_mimo_fw.hip: one realization (4 x 4) / two realizations (2 x 2) per wavefront at fft_size 256, complex128
-int run_mimo_ofdm_fw(mcle_ctx* ctx, int dtype, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
-                     mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit);
-int run_mimo_ofdm_planar(mcle_ctx* ctx, int dtype, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
-                      mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit);
-int run_mimo_ofdm_mfma(mcle_ctx* ctx, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
-                       mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit);
+// the config-4 families (pipeline_mimo_{mfma,planar,fw,qw,pw}.hip): each launches the instantiation a plan of its family names
+#define MCLE_C4_LAUNCHER(name)                                                                                                  \
+    int name(mcle_ctx* ctx, const C4Plan& plan, const mcle_mimo_ofdm_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count, \
+             mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit)
+MCLE_C4_LAUNCHER(launch_mimo_ofdm_mfma);
+MCLE_C4_LAUNCHER(launch_mimo_ofdm_planar);
+MCLE_C4_LAUNCHER(launch_mimo_ofdm_fw);
+MCLE_C4_LAUNCHER(launch_mimo_ofdm_qw);
+MCLE_C4_LAUNCHER(launch_mimo_ofdm_pw);
+#undef MCLE_C4_LAUNCHER
 // pipeline_siso_tdl.hip
 int run_ofdm_tdl_batched(mcle_ctx* ctx, int dtype, const mcle_ofdm_tdl_cfg* cfg, uint64_t seed, uint64_t first,
                          uint64_t count, mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit);
@@ -1171,39 +1173,36 @@ int mcle_run_mimo_ofdm(mcle_ctx* ctx, int dtype, const mcle_mimo_ofdm_cfg* cfg, 
     MCLE_REQUIRE(count <= 0x7fffffffull, "at most 2^31-1 realizations per call");
     if (count == 0) return MCLE_OK;
     if ((rc = ctx->bind())) return rc;
-    if (dtype == MCLE_F32 && ctx->opt[MCLE_OPT_F32_MFMA] && !ctx->opt[MCLE_OPT_NO_MFMA]) {   // matrix-core kernel on request (1024, 4x4)
-        rc = run_mimo_ofdm_mfma(ctx, cfg, seed, first, count, d_counters, d_sym_err, d_bit_err);
-        if (rc != MCLE_E_UNSUPPORTED) return rc;
+    // which kernel: c4_select.hpp, from the shape, the link and the options alone
+    C4Query q{};
+    q.f64 = dtype == MCLE_F64;
+    q.fft_size = cfg->fft_size, q.nt = cfg->nt, q.nr = cfg->nr, q.num_used = cfg->num_used, q.cp_size = cfg->cp_size;
+    q.M = ctx->M;
+    {
+        ModemParams<double> mp = pipe_modem<double>(ctx, cfg->demod_method);
+        q.dec = walk_dec_kind(ctx, mp);
     }
-    // the planar kernel family (pipeline_mimo_planar.hip: FFT 256 .. 2048, 1 <= Nt <= Nr <= 4).  no_mfma = 1 (complex64) and f64_generic = 1
-    // (either arithmetic) keep the call on the round-1 generic kernel below WHERE THAT ONE EXISTS (Nt = Nr in {2, 4}); every other
-    // geometry still runs the planar family -- an option selects a kernel, it does not shrink the envelope
-    const bool generic_has_it = cfg->nt == cfg->nr && (cfg->nt == 2 || cfg->nt == 4);
-    const bool want_generic = generic_has_it && (ctx->opt[MCLE_OPT_F64_GENERIC] || (dtype == MCLE_F32 && ctx->opt[MCLE_OPT_NO_MFMA]));
-    // 2x2 at 256 points: the generic kernel (four realizations per 256-thread workgroup) is the faster one -- 1.65 against 1.06e8
-    // realizations/s in complex64, 1.01 against 0.98e8 in complex128 (profiles/r05/f32_family_rates.json, f64_family_rates.json): the
-    // planar family has no kernel of this shape
-    const bool generic_is_faster = cfg->fft_size == 256 && cfg->nt == 2 && cfg->nr == 2;
-    if (generic_is_faster && !want_generic) {
-        // ... and since round 6 the full-wave kernel (pipeline_mimo_fw.hip, two realizations per wavefront) beats both inside its envelope
-        const long long thr = ctx->opt[MCLE_OPT_F64_THREADS];
-        if (thr == 0 || thr == 260 || thr == 262) {
-            rc = run_mimo_ofdm_fw(ctx, dtype, cfg, seed, first, count, d_counters, d_sym_err, d_bit_err);
-            if (rc != MCLE_E_UNSUPPORTED) return rc;
-        }
+    q.f64_threads = ctx->opt[MCLE_OPT_F64_THREADS], q.f64_generic = ctx->opt[MCLE_OPT_F64_GENERIC];
+    q.no_mfma = ctx->opt[MCLE_OPT_NO_MFMA], q.f32_mfma = ctx->opt[MCLE_OPT_F32_MFMA], q.mfma_variant = ctx->opt[MCLE_OPT_MFMA_VARIANT];
+#ifdef MCLE_EXPERIMENTS
+    q.f64_variant = ctx->opt[MCLE_OPT_F64_VARIANT];
+#endif
+    const C4Plan plan = c4_select(q);
+    switch (plan.family) {
+        case C4_MFMA: return launch_mimo_ofdm_mfma(ctx, plan, cfg, seed, first, count, d_counters, d_sym_err, d_bit_err);
+        case C4_PLANAR: return launch_mimo_ofdm_planar(ctx, plan, cfg, seed, first, count, d_counters, d_sym_err, d_bit_err);
+        case C4_FW: return launch_mimo_ofdm_fw(ctx, plan, cfg, seed, first, count, d_counters, d_sym_err, d_bit_err);
+        case C4_QW: return launch_mimo_ofdm_qw(ctx, plan, cfg, seed, first, count, d_counters, d_sym_err, d_bit_err);
+        case C4_PW: return launch_mimo_ofdm_pw(ctx, plan, cfg, seed, first, count, d_counters, d_sym_err, d_bit_err);
+        case C4_GENERIC: break;
+        default:
+            MCLE_REQUIRE(false, "fused MIMO pipeline: %d x %d at fft_size %d is outside the envelope (2x2 / 4x4 at 64 .. 2048 in both arithmetics; "
+                         "every 1 <= Nt <= Nr <= 4 with Nr >= 2 at 256 .. 2048)", cfg->nt, cfg->nr, cfg->fft_size);
     }
-    if (!want_generic && !generic_is_faster) {
-        rc = run_mimo_ofdm_planar(ctx, dtype, cfg, seed, first, count, d_counters, d_sym_err, d_bit_err);
-        if (rc != MCLE_E_UNSUPPORTED) return rc;
-    }
-    MCLE_REQUIRE(cfg->nt == cfg->nr && (cfg->nt == 2 || cfg->nt == 4),
-                 "fused MIMO pipeline: %d x %d at fft_size %d is outside the envelope (2x2 / 4x4 at 64 .. 2048 in both arithmetics; "
-                 "every 1 <= Nt <= Nr <= 4 with Nr >= 2 at 256 .. 2048)", cfg->nt, cfg->nr, cfg->fft_size);
-#define MCLE_RUN(N_, NA_)                                                                                         \
-    if (cfg->fft_size == N_ && cfg->nt == NA_)                                                                    \
-        return dtype == MCLE_F32                                                                                  \
-                   ? run_mimo_impl<float, N_, NA_>(ctx, cfg, seed, first, count, d_counters, d_sym_err, d_bit_err) \
-                   : run_mimo_impl<double, N_, NA_>(ctx, cfg, seed, first, count, d_counters, d_sym_err, d_bit_err);
+#define MCLE_RUN(N_, NA_)                                                                                               \
+    if (plan.n == N_ && plan.nt == NA_)                                                                                 \
+        return plan.f64 ? run_mimo_impl<double, N_, NA_>(ctx, plan, cfg, seed, first, count, d_counters, d_sym_err, d_bit_err) \
+                        : run_mimo_impl<float, N_, NA_>(ctx, plan, cfg, seed, first, count, d_counters, d_sym_err, d_bit_err);
     MCLE_RUN(64, 2) MCLE_RUN(64, 4) MCLE_RUN(128, 2) MCLE_RUN(128, 4) MCLE_RUN(256, 2) MCLE_RUN(256, 4)
     MCLE_RUN(512, 2) MCLE_RUN(512, 4) MCLE_RUN(1024, 2) MCLE_RUN(1024, 4) MCLE_RUN(2048, 2) MCLE_RUN(2048, 4)
 #undef MCLE_RUN

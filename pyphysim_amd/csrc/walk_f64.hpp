@@ -38,9 +38,7 @@
 
 namespace mcle {
 
-enum : int { WDEC_GENERIC = 0, WDEC_SLICER = 1, WDEC_QAM_CERT = 2, WDEC_QUAD_CERT = 3, WDEC_AXIS4_CERT = 4 };
-
-// host: the decision form a launch with these modem parameters compiles to (and, for the on-axis four-point form -- the
+// host: the decision form (WDEC_*: c4_select.hpp) a launch with these modem parameters compiles to (and, for the on-axis four-point form -- the
 // reference's PSK(4), which has no entry in ModemParams::cert -- its constants in the quadrant certificate's fields)
 template <typename T> inline int walk_dec_kind(const mcle_ctx* ctx, ModemParams<T>& mp) {
     if (mp.method == MCLE_DEMOD_QAM_SLICER) return WDEC_SLICER;

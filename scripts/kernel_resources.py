@@ -32,7 +32,7 @@ KEYS = (".vgpr_count", ".agpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr
 # What the dispatchers pick with every option at 0 ("default": true): regular expressions over the demangled kernel names.
 # Everything else in the library is reachable through an option (A/B runs, kernel-vs-kernel tests) or outside a default's envelope.
 DEFAULT = [
-    # config 4 family (pipeline_mimo_planar.hip: run_mimo_ofdm_planar_t): 1024 with four receive antennas = radix-16 passes
+    # config 4 family (csrc/c4_select.hpp: c4_select): 1024 with four receive antennas = radix-16 passes
     # (complex128 fused, two per SIMD; complex64 unfused, four), every other shape the radix-4 table
     # (round 6: complex128 4 x 4 inside the full-band / even-prefix / certificate envelope = the part-wave kernels -- pw<NW, decision form,
     #  wavefronts per SIMD, 0>: 512 / 1024 at three, 2048 at two -- and at 256 the full-wave kernel fw<antennas, decision form, 3, 0>,

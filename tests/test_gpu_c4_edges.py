@@ -2,13 +2,13 @@
 served each call named (Engine.last_kernel(), grammar at mcle_ctx_last_kernel in include/mcle.h) and its per-realization counts
 against the oracle chain (oracle/chains.py::chain_mimo_ofdm) under the same Philox keying.
 
-A call falls through a tree (csrc/pipelines.hip::mcle_run_mimo_ofdm -> pipeline_mimo_planar.hip::run_mimo_ofdm_planar_t):
+The selection is a tree (csrc/c4_select.hpp::c4_select, called by csrc/pipelines.hip::mcle_run_mimo_ofdm):
   complex64 with f32_mfma = 1 (and no_mfma = 0) at (1024, 4 x 4)                      -> mimo_ofdm_mfma v<variant>
   Nt = Nr in {2, 4} with f64_generic = 1, or complex64 with no_mfma = 1               -> mimo_ofdm_generic<N,NA> (64 .. 2048)
   (256, 2 x 2): f64_threads in {0, 260, 262} inside the wave envelope                 -> mimo_ofdm_fw<2>, else the generic kernel
   (256, 4 x 4): the same                                                              -> mimo_ofdm_fw<4>, else the planar kernel
-  complex128 (512 / 2048, 4 x 4): f64_threads in {0, 260, 262, 265} inside the envelope -> mimo_ofdm_pw<2 / 8>, else planar
-  complex128 (1024, 4 x 4): {0, 263, 264, 265} -> mimo_ofdm_pw<4>; {0, 260, 262} inside the quarter-wave envelope -> mimo_ofdm_qw;
+  complex128 (512 / 2048, 4 x 4): f64_threads in {0, 260, 262, 265 .. 268} inside the envelope -> mimo_ofdm_pw<2 / 8>, else planar
+  complex128 (1024, 4 x 4): {0, 263, 264, 265 .. 268} -> mimo_ofdm_pw<4>; {0, 260, 262} inside the quarter-wave envelope -> mimo_ofdm_qw;
                             258 / 256 / 512 / 257 / anything else -> five planar forms (complex64: 256 / 512 / 259 / 257 / else)
   every 1 <= Nt <= Nr <= 4 with Nr >= 2 at 256 .. 2048                                -> the planar geometry table
   Nt = Nr in {2, 4} at 64 / 128 (and what fell through above)                         -> the generic kernel;  anything else: refused.
@@ -16,7 +16,8 @@ The wave envelope: full band, even cyclic prefix, decisions by the slicer or a c
 points on the axes); the quarter-wave kernel has no on-axis certificate.  demod_nocert = 1 takes the certificates away, so
 min-distance calls leave the wave kernels.
 
-c4_tag() below replays that tree on the host FROM THE DISPATCHER'S CONDITIONS (it never calls the library); every row of ROWS names the
+c4_tag() below replays that tree on the host as an INDEPENDENT statement of it (it never calls the library, and
+tests/test_c4_select_cpu.py holds the C++ selection against it over the whole cross product); every row of ROWS names the
 tag it expects, a CPU test proves that the rows cover every tag the replay can produce over the whole cross product of shapes,
 arithmetics and options and that every row agrees with the replay, and one GPU walker per row asserts the tag, the counts against the
 oracle (complex128 exact; complex64 by the criteria of test_gpu_planar_f32.py::_close), and the counts bit-identical under splits of
@@ -39,7 +40,7 @@ SKIPPED = 0xFFFFFFFF                                  # a skipped realization's 
 REFUSED = "refused"
 SIZES = (64, 128, 256, 512, 1024, 2048)
 PAIRS = tuple((nt, nr) for nr in range(1, 5) for nt in range(1, nr + 1))             # the Nt <= Nr <= 4 triangle: 10 pairs
-THREADS = (0, 256, 257, 258, 259, 260, 261, 262, 263, 264, 265, 512, 1024)           # every value mcle_ctx_set_option accepts
+THREADS = (0, 256, 257, 258, 259, 260, 261, 262, 263, 264, 265, 266, 267, 268, 512, 1024)      # every value mcle_ctx_set_option accepts
 COUNTERS = ("sym_errors", "sym_errors_sq", "bit_errors", "bit_errors_sq", "n_realizations", "n_skipped")
 
 # ---- link cases: (constellation, SNR, prefix, band, demodulator).  "used": None = full band, an int = that many FEWER subcarriers,
@@ -88,8 +89,8 @@ def FW(na, dt, w):
     return "mimo_ofdm_fw<%d> %s w%d" % (na, dt, w)
 
 
-def PW(nw, form, two=False):
-    return "mimo_ofdm_pw<%d>/%s%s" % (nw, form, "/w2" if two else "")
+def PW(nw, form, two=False, sfx=""):
+    return "mimo_ofdm_pw<%d>/%s%s%s" % (nw, form, "/w2" if two else "", sfx)
 
 
 def QW(w):
@@ -124,24 +125,24 @@ def dec_kind(link):
 
 
 def wave_envelope(link, fft):
-    """run_mimo_ofdm_fw / run_mimo_ofdm_pw: full band, even prefix, M <= 256, a decision form."""
+    """The wave kernels (full-wave, part-wave): full band, even prefix, M <= 256, a decision form."""
     return _used(link, fft) == fft and _cp(link) % 2 == 0 and link["M"] <= 256 and dec_kind(link) != DEC_GENERIC
 
 
 def qw_envelope(link, fft):
-    """run_mimo_ofdm_qw: as above, but only the slicer or a modem_cert certificate (no on-axis form)."""
+    """The quarter-wave kernel: as above, but only the slicer or a modem_cert certificate (no on-axis form)."""
     return _used(link, fft) == fft and _cp(link) % 2 == 0 and link["M"] <= 256 and dec_kind(link) in (DEC_SLICER, DEC_QAM, DEC_QUAD)
 
 
 def planar_wps(dt, n, nt, nr, w64):
-    """pipeline_mimo_planar.hip::planar_wps: complex64 takes two more wavefronts per SIMD at 256 points (not 4 x 4) and (512, Nr = 2)."""
+    """c4_select.hpp::planar_wps: complex64 takes two more wavefronts per SIMD at 256 points (not 4 x 4) and (512, Nr = 2)."""
     if dt == "f32" and w64 <= 3 and ((n == 256 and not (nt == 4 and nr == 4)) or (n == 512 and nr == 2)):
         return w64 + 2
     return w64
 
 
 def _geom(dt, n, nt, nr, w2, w4):
-    """MCLE_F64_SIZE / MCLE_F64_GEOM: Nr = 2 / 4 two antennas per thread, Nr = 3 three (one group)."""
+    """The planar radix-4 geometry table: Nr = 2 / 4 two antennas per thread, Nr = 3 three (one group)."""
     if nr == 2:
         return PL(n, nt, nr, dt, 2, planar_wps(dt, n, nt, nr, w2))
     if nr == 3:
@@ -156,23 +157,27 @@ def fw_tag(dt, na, thr):
     return FW(na, dt, (3 if two else 2) if dt == "f32" else (2 if two else 3))
 
 
+PW_SUFFIX = {266: "/a", 267: "/x", 268: "/h"}
+
+
 def pw_tag(n, thr):
     td, two = thr == 265, thr in (262, 264)
+    sfx = PW_SUFFIX.get(thr, "")                       # 266 / 267 / 268: the default form with another map or exchange, asked for by value
     if n == 2048:
-        return PW(8, "time" if td else "freq")
-    return PW(n // 256, "time") if td else PW(n // 256, "freq", two)
+        return PW(8, "time" if td else "freq", sfx=sfx)
+    return PW(n // 256, "time") if td else PW(n // 256, "freq", two, sfx)
 
 
 def planar_family(dt, n, nt, nr, link, thr):
-    """run_mimo_ofdm_planar_t; None = MCLE_E_UNSUPPORTED."""
+    """The wave kernels at 4 x 4 and the planar family (c4_select_planar); None = no kernel of this shape here."""
     f64 = dt == "f64"
     if n == 256 and nt == 4 and nr == 4 and thr in (0, 260, 262) and wave_envelope(link, n):
         return fw_tag(dt, 4, thr)
-    if n in (512, 2048) and nt == 4 and nr == 4 and f64 and thr in (0, 260, 262, 265) and wave_envelope(link, n):
+    if n in (512, 2048) and nt == 4 and nr == 4 and f64 and thr in (0, 260, 262, 265, 266, 267, 268) and wave_envelope(link, n):
         return pw_tag(n, thr)
     if n == 1024 and nt == 4 and nr == 4:
         if f64:
-            if thr in (0, 263, 264, 265) and wave_envelope(link, n):
+            if thr in (0, 263, 264, 265, 266, 267, 268) and wave_envelope(link, n):
                 return pw_tag(n, thr)
             if thr in (0, 260, 262) and qw_envelope(link, n):
                 return QW(2 if thr == 262 else 3)
@@ -352,6 +357,15 @@ for dt_ in BOTH:
 # no_mfma = 1 in complex64 at a shape without a generic kernel: the planar family
 row(1024, 2, 4, "f32", "in", PL(1024, 2, 4, "f32", 4, 4, 4), no_mfma=1)
 row(512, 3, 3, "f32", "in", PL(512, 3, 3, "f32", 3, 2), no_mfma=1)
+
+# f64_threads = 266 / 267 / 268 (appended: the rows above keep their numbers): the part-wave kernel's default form with the ownership
+# map of rounds 6 - 9 ("/a"), with the exchange by re / im planes ("/x") or in complex halves ("/h") asked for, at all three sizes;
+# outside the envelope the planar kernel the default lands on; complex64 has no part-wave kernel
+for thr_, n_ in itertools.product((266, 267, 268), (512, 1024, 2048)):
+    row(n_, 4, 4, "f64", "in", PW(n_ // 256, "freq", sfx=PW_SUFFIX[thr_]), f64_threads=thr_)
+    row(n_, 4, 4, "f64", "cp15", {512: PL(512, 4, 4, "f64", 2, 3), 1024: P16, 2048: PL(2048, 4, 4, "f64", 4, 2)}[n_], f64_threads=thr_)
+    row(n_, 4, 4, "f32", "in", {512: PL(512, 4, 4, "f32", 2, 3), 1024: PL(1024, 4, 4, "f32", 4, 4, 4), 2048: PL(2048, 4, 4, "f32", 4, 2)}[n_],
+        f64_threads=thr_)
 
 
 def _row_id(i):
