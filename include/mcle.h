@@ -945,6 +945,49 @@ typedef struct mcle_pilot_mse_cfg {
 int mcle_run_pilot_mse(mcle_ctx* ctx, int dtype, const mcle_pilot_mse_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
                        double* d_err_ls, double* d_err_mmse, double* d_pow);
 
+/* Flat MIMO (Blast) link with pilot-estimated channel state next to perfect channel state (csrc/pipeline_mimo_pilot.hip): what an
+ * estimation error costs in symbol and bit errors.  One realization: H = alpha L W (W nr x nt of CN(0, 1); L = I when
+ * d_chan_factor is NULL); a pilot block s [nt][n_pilots] of power pilot_power (drawn, s = sqrt(pilot_power) e^{2 pi j u}, or
+ * d_pilots); Y_p = H s + sqrt(noise_var) N_p; the estimate
+ *     LS:    H^ = Y_p s^H (s s^H)^-1
+ *     MMSE:  h^ = B (Y_p s^H) n_pilots / |s|^2, nt = 1, B = (noise_var I + n_pilots C)^-1 C formed by the caller in f64;
+ * then the data of mcle_run_mimo_flat(MCLE_MIMO_BLAST): X = reshape(sym, (nt, -1), 'F') / sqrt(nt), Y = H X + sqrt(noise_var) N,
+ * est = G Y with G = sqrt(nt) solve(A^H A + nu I, A^H) (nu = noise_var if mmse_filter else 0; pinv(A) at nu = 0) for A = H^
+ * (d_counters[0], estimated CSI) and for A = H (d_counters[1], perfect CSI).  Both filters see the same symbols and the same
+ * noise samples: one walk over the data, one noise draw.  A realization whose pilot Gram matrix (a pivot at or below 1e-12 of
+ * its trace) or either filter is numerically singular is skipped in BOTH blocks (n_skipped; 0xFFFFFFFF in the per-realization
+ * arrays).
+ * Envelope: 1 <= nt <= nr <= 4; nt <= n_pilots <= 256; n_symbols >= 1; noise_var >= 0; pilot_power > 0; alpha finite; the MMSE
+ * estimator needs nt = 1 and d_mmse_matrix; fixed pilots (random_pilots = 0) need d_pilots; count <= 2^31-1.  Anything else
+ * returns MCLE_E_INVAL with a message naming the rule; count = 0 returns MCLE_OK and launches nothing.
+ * d_pilots [nt][n_pilots], d_chan_factor [nr][nr], d_mmse_matrix [nr][nr]: DEVICE, row-major complex128 (interleaved re, im)
+ * whatever `dtype`: the channel, the pilot block, the estimate and both filters are formed in f64 per realization (the inverse
+ * Gram matrix of a fixed pilot block once per call, on the host); `dtype` is the arithmetic of the walk over the data.
+ * d_sym_err, d_bit_err: NULL or [2][count] (block 0 then block 1); d_err, d_pow: NULL or [count], |H^ - H|_F^2 and |H|_F^2 (f64;
+ * unspecified for a skipped realization).  Nothing depends on the grid, on MCLE_OPT_GRID_OVERSUB or on how
+ * [first, first + count) is split.
+ * Draws (mcle-philox-v1), realization first + r of `seed`:
+ *     W[r][a]             stream 2 (CHAN)    CN sample r nt + a                     as mcle_run_mimo_flat
+ *     data symbol         stream 0 (DATA)    n = t nt + a                           as mcle_run_mimo_flat
+ *     data noise (r, t)   stream 1 (NOISE)   CN sample r n_symbols + t              as mcle_run_mimo_flat
+ *     pilot phase (a, p)  stream 3 (PHASE)   uniform a n_pilots + p                 random pilots only
+ *     pilot noise (r, p)  stream 4 (PILOT)   CN sample 2 ceil(n_pilots / 2) r + p
+ * so with L = I and alpha = 1 block 1 is mcle_run_mimo_flat(MCLE_MIMO_BLAST) on the same (seed, realization).
+ * mcle_ctx_last_kernel: "mimo_pilot_link f64|f32 ls|mmse". */
+typedef struct mcle_mimo_pilot_cfg {
+    int32_t nt, nr;            /* 1 <= nt <= nr <= 4 */
+    int32_t n_pilots;          /* nt .. 256 */
+    int32_t n_symbols;         /* NSymbs per layer, >= 1 */
+    int32_t demod_method;
+    int32_t estimator;         /* 0 LS, 1 MMSE (nt = 1, d_mmse_matrix required) */
+    int32_t random_pilots;     /* 1: drawn per realization; 0: d_pilots [nt][n_pilots] */
+    int32_t mmse_filter;       /* noise_var goes into the Blast filter (set_noise_var) */
+    double noise_var, pilot_power, alpha;
+} mcle_mimo_pilot_cfg;
+int mcle_run_mimo_pilot_link(mcle_ctx* ctx, int dtype, const mcle_mimo_pilot_cfg* cfg, uint64_t seed, uint64_t first,
+                             uint64_t count, const double* d_pilots, const double* d_chan_factor, const double* d_mmse_matrix,
+                             mcle_counters* d_counters, uint32_t* d_sym_err, uint32_t* d_bit_err, double* d_err, double* d_pow);
+
 /* ---- Grassmannian codebooks: chordal distances and the random search (subspace/metrics.py:21-113 calc_principal_angles,
  *      calc_chordal_distance_from_principal_angles; apps/find_codebook.py:73-231 CodebookFinder) ---------------------------
  * A codebook is K precoders [Nt][Ns], row-major, complex of the call's dtype.  Q_k: an orthonormal basis of the column space of

@@ -15,7 +15,7 @@ MCLE_F32, MCLE_F64 = 0, 1
 DEMOD_MINDIST, DEMOD_QAM_SLICER = 0, 1
 CONST_GENERIC, CONST_QAM, CONST_BPSK = 0, 1, 2
 MAX_TAPS = 24
-STREAM_DATA, STREAM_NOISE, STREAM_CHAN, STREAM_PHASE = 0, 1, 2, 3
+STREAM_DATA, STREAM_NOISE, STREAM_CHAN, STREAM_PHASE, STREAM_PILOT = 0, 1, 2, 3, 4
 # mcle_ctx_set_option keys (include/mcle.h MCLE_OPT_*): kernel selection for A/B runs and kernel-vs-kernel tests
 OPTIONS = {"no_mfma": 0, "mfma_variant": 1, "grid_oversub": 2, "flat_wgs_per_cu": 3, "single_tdl": 4,
            "tdl_mfma_waves": 5, "jakes_direct": 6, "f64_generic": 7,
@@ -154,6 +154,15 @@ class PilotMseCfg(Structure):
                 ("d_pilots", c_void_p), ("chan_factor", POINTER(c_double)), ("cov", POINTER(c_double))]
 
 
+class MimoPilotCfg(Structure):
+    _fields_ = [("nt", c_int32), ("nr", c_int32), ("n_pilots", c_int32), ("n_symbols", c_int32), ("demod_method", c_int32),
+                ("estimator", c_int32), ("random_pilots", c_int32), ("mmse_filter", c_int32), ("noise_var", c_double),
+                ("pilot_power", c_double), ("alpha", c_double)]
+
+
+PILOT_ESTIMATORS = {"ls": 0, "mmse": 1}
+
+
 class CodebookCfg(Structure):
     _fields_ = [("K", c_int32), ("Nt", c_int32), ("Ns", c_int32), ("type", c_int32)]
 
@@ -283,6 +292,8 @@ _PROTOS = {
     "mcle_ls_estimate": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_size_t, _P]),
     "mcle_mmse_estimate": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, c_size_t, c_double, POINTER(c_double), _P]),
     "mcle_run_pilot_mse": (c_int, [_P, c_int, POINTER(PilotMseCfg), c_uint64, c_uint64, c_uint64, _P, _P, _P]),
+    "mcle_run_mimo_pilot_link": (c_int, [_P, c_int, POINTER(MimoPilotCfg), c_uint64, c_uint64, c_uint64, _P, _P, _P, _P, _P, _P, _P,
+                                         _P]),
     "mcle_chordal_min_dist": (c_int, [_P, c_int, _P, c_size_t, c_int, c_int, c_int, _P, _P, _P]),
     "mcle_codebook_generate": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_uint64, c_uint64, c_uint64, _P]),
     "mcle_run_codebook_search": (c_int, [_P, c_int, POINTER(CodebookCfg), c_uint64, c_uint64, c_uint64, POINTER(CodebookResult),

@@ -1,0 +1,600 @@
+// pipeline_mimo_pilot.hip -- the flat MIMO (Blast) link with pilot-estimated channel state, next to perfect channel state.
+// Reference: channel_estimation/estimators.py:12-61 compute_ls_estimation, :100-174 compute_mmse_estimation (Fodor et al. 2014)
+// in front of mimo/mimo.py:463-660 Blast.  Per realization
+//     H = alpha L W,   Y_p = H s + sqrt(noise_var) N_p,   H^ = Y_p s^H (s s^H)^-1   (LS)
+//                                                         h^ = B (Y_p s^H) P / |s|^2 (MMSE, nt = 1; B formed by the caller)
+// then the Blast receive filter from H^ (counter block 0) and from H (counter block 1), and ONE walk over the data symbols:
+// both filters see the same symbols and the same noise samples, so the two error counts differ by the estimation error alone
+// and the complex128 Box-Muller is paid once.
+//
+// Two launches, as pipeline_mimo_flat.hip: k_mimo_pilot_setup, one realization per lane, everything in f64 (the channel, the
+// pilot block accumulated pilot by pilot -- nothing of size P stays live --, an nt x nt Hermitian Cholesky of the Gram matrix, two
+// Blast filters); k_mimo_pilot_link, four independent wavefronts per workgroup, each walking the symbol columns of a chunk of
+// realizations from their records.  Record per realization, rounded to the link's arithmetic:
+//     A_est = G^ H / sqrt(nt) [4][4], G^ [4][4], A_perf = G H / sqrt(nt) [4][4], G [4][4], {ok, 0}.
+// |H^ - H|_F^2 and |H|_F^2 leave the set-up kernel as f64 whatever the link's arithmetic.
+//
+// Draw ledger (mcle-philox-v1), realization first + r of `seed`:
+//     W[r][a]               CHAN (2)    CN sample r nt + a                      as mcle_run_mimo_flat
+//     data symbol           DATA (0)    n = t nt + a                            as mcle_run_mimo_flat
+//     data noise (r, t)     NOISE (1)   CN sample r n_symbols + t               as mcle_run_mimo_flat
+//     pilot phase (a, p)    PHASE (3)   uniform a P + p                         random pilots only
+//     pilot noise (r, p)    PILOT (4)   CN sample 2 ceil(P / 2) r + p           (a Philox block = pilots 2 j, 2 j + 1 of one antenna)
+// With L = I and alpha = 1 counter block 1 is mcle_run_mimo_flat(MCLE_MIMO_BLAST) on the same (seed, realization).
+#include <cmath>
+#include <complex>
+#include <vector>
+
+#include "mimo.hpp"
+#include "modem.hpp"
+#include "philox.hpp"
+#include "pipe_common.hpp"
+#include "qam_pack.hpp"
+#include "totals.hpp"
+#include "wave_draws.hpp"
+
+namespace mcle {
+
+constexpr int kPilotMax = 4;                                   // antennas per side
+constexpr int kPilotMaxPilots = 256;
+constexpr int kPilotSet = 2 * kPilotMax * kPilotMax;           // A [4][4] then G [4][4] of one filter
+constexpr int kPilotRec = 2 * kPilotSet + 1;                   // estimated CSI, perfect CSI, {ok, 0}
+// a Gram pivot at or below this share of the Gram matrix's trace counts as singular (host and device alike)
+constexpr double kPilotPivotFloor = 1e-12;
+
+struct PilotSetup {
+    int P, half;                                // half = ceil(P / 2)
+    int random_pilots, mmse_est, gram_ok;
+    double amp, sigma, alpha, filter_nv;        // sqrt(pilot_power), sqrt(noise_var)
+    double2 ginv[kPilotMax * kPilotMax];        // fixed pilots: (s s^H)^-1, entry [a][b] at a * kPilotMax + b
+};
+
+template <typename T, int NT, int NR>
+__global__ __launch_bounds__(64) void k_mimo_pilot_setup(PilotSetup p, const double2* __restrict__ pilots,
+                                                         const double2* __restrict__ Lm, const double2* __restrict__ Bm,
+                                                         uint64_t seed, uint64_t first, uint64_t count,
+                                                         cx<T>* __restrict__ recs, double* __restrict__ err_out,
+                                                         double* __restrict__ pow_out) {
+    const uint64_t rl = (uint64_t)blockIdx.x * 64 + threadIdx.x;
+    if (rl >= count) return;
+    const Rng rng(seed, first + rl);
+    const double2 zero = mk<double>(0, 0);
+    // ---- H = alpha L W
+    double2 H[NR][NT];
+#pragma unroll
+    for (int r = 0; r < NR; ++r)
+#pragma unroll
+        for (int a = 0; a < NT; ++a) H[r][a] = cn_sample<double>(rng, STREAM_CHAN, (uint64_t)(r * NT + a), 1.0);
+    if (Lm) {
+        double2 W[NR][NT];
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+#pragma unroll
+            for (int a = 0; a < NT; ++a) W[r][a] = H[r][a];
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+#pragma unroll
+            for (int a = 0; a < NT; ++a) {
+                double2 acc = zero;
+#pragma unroll
+                for (int k = 0; k < NR; ++k) acc = cfma4(Lm[r * NR + k], W[k][a], acc);
+                H[r][a] = acc;
+            }
+    }
+#pragma unroll
+    for (int r = 0; r < NR; ++r)
+#pragma unroll
+        for (int a = 0; a < NT; ++a) H[r][a] = cscale(H[r][a], p.alpha);      // (alpha = 1: exact)
+    // ---- the pilot block, two pilots (one PILOT block per antenna) a trip: R = Y_p s^H, Gram = s s^H (lower triangle)
+    double2 R[NR][NT], Gm[NT][NT];
+#pragma unroll
+    for (int r = 0; r < NR; ++r)
+#pragma unroll
+        for (int a = 0; a < NT; ++a) R[r][a] = zero;
+#pragma unroll
+    for (int a = 0; a < NT; ++a)
+#pragma unroll
+        for (int b = 0; b < NT; ++b) Gm[a][b] = zero;
+    for (int j = 0; j < p.half; ++j) {
+        double2 n[2][NR];
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+            n[0][r] = n[1][r] = zero;
+            if (p.sigma != 0.0) cn_pair<double>(rng, STREAM_PILOT, (uint32_t)(r * p.half + j), p.sigma, n[0][r], n[1][r]);
+        }
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int pp = 2 * j + e;
+            if (pp >= p.P) break;
+            double2 s[NT];
+#pragma unroll
+            for (int a = 0; a < NT; ++a) {
+                if (p.random_pilots) {
+                    const double u = uniform_at(rng, STREAM_PHASE, (uint64_t)(a * p.P + pp));
+                    double sn, cs;
+                    sincospi(2.0 * u, &sn, &cs);
+                    s[a] = mk<double>(p.amp * cs, p.amp * sn);
+                } else {
+                    s[a] = pilots[a * p.P + pp];
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < NR; ++r) {
+                double2 y = n[e][r];
+#pragma unroll
+                for (int a = 0; a < NT; ++a) y = cfma4(H[r][a], s[a], y);
+#pragma unroll
+                for (int a = 0; a < NT; ++a) R[r][a] = cx_macc(R[r][a], y, s[a]);
+            }
+            if (p.random_pilots) {
+#pragma unroll
+                for (int a = 0; a < NT; ++a)
+#pragma unroll
+                    for (int b = 0; b <= a; ++b) Gm[a][b] = cx_macc(Gm[a][b], s[a], s[b]);
+            }
+        }
+    }
+    // ---- H^ = R Gram^-1
+    double2 Hest[NR][NT];
+    bool ok = true;
+    double inv_s2 = p.ginv[0].x;                 // nt = 1: 1 / |s|^2
+    if (p.random_pilots) {
+        double tr = 0.0;
+#pragma unroll
+        for (int a = 0; a < NT; ++a) tr += Gm[a][a].x;
+        // Gram = C C^H, C lower triangular
+        double2 C[NT][NT];
+        double invd[NT];
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+#pragma unroll
+            for (int i = j; i < NT; ++i) {
+                double2 a = Gm[i][j];
+#pragma unroll
+                for (int k = 0; k < j; ++k) a = csub(a, cmulc(C[i][k], C[j][k]));
+                if (i == j) {
+                    ok = ok && (a.x > kPilotPivotFloor * tr);
+                    C[j][j] = mk<double>(sqrt(a.x), 0.0);
+                    invd[j] = 1.0 / C[j][j].x;
+                } else {
+                    C[i][j] = cscale(a, invd[j]);
+                }
+            }
+        }
+        inv_s2 = invd[0] * invd[0];
+        // a row x of H^ solves x C C^H = R[r]: y C^H = R[r] forwards, x C = y backwards
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+            double2 y[NT];
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+                double2 v = R[r][j];
+#pragma unroll
+                for (int k = 0; k < j; ++k) v = csub(v, cmulc(y[k], C[j][k]));
+                y[j] = cscale(v, invd[j]);
+            }
+#pragma unroll
+            for (int j = NT - 1; j >= 0; --j) {
+                double2 v = y[j];
+#pragma unroll
+                for (int k = j + 1; k < NT; ++k) v = csub(v, cmul(y[k], C[k][j]));
+                y[j] = cscale(v, invd[j]);
+            }
+#pragma unroll
+            for (int a = 0; a < NT; ++a) Hest[r][a] = y[a];
+        }
+    } else {
+        ok = p.gram_ok != 0;
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+#pragma unroll
+            for (int b = 0; b < NT; ++b) {
+                double2 acc = zero;
+#pragma unroll
+                for (int a = 0; a < NT; ++a) acc = cfma4(R[r][a], p.ginv[a * kPilotMax + b], acc);
+                Hest[r][b] = acc;
+            }
+    }
+    if constexpr (NT == 1) {
+        if (p.mmse_est) {                        // h^ = B (Y_p s^H) P / |s|^2
+            const double scale = (double)p.P * inv_s2;
+#pragma unroll
+            for (int r = 0; r < NR; ++r) {
+                double2 acc = zero;
+#pragma unroll
+                for (int k = 0; k < NR; ++k) acc = cfma4(Bm[r * NR + k], R[k][0], acc);
+                Hest[r][0] = cscale(acc, scale);
+            }
+        }
+    }
+    double err = 0.0, pw = 0.0;
+#pragma unroll
+    for (int r = 0; r < NR; ++r)
+#pragma unroll
+        for (int a = 0; a < NT; ++a) {
+            const double2 d = csub(Hest[r][a], H[r][a]);
+            err += d.x * d.x + d.y * d.y;
+            pw += H[r][a].x * H[r][a].x + H[r][a].y * H[r][a].y;
+        }
+    if (err_out) err_out[rl] = err;
+    if (pow_out) pow_out[rl] = pw;
+    // ---- the two filters and the record: A = G (H / sqrt(nt)), the association of k_mimo_flat_setup
+    cx<T>* rec = recs + rl * kPilotRec;
+    const double w = 1.0 / sqrt((double)NT);
+    double2 HW[NR][NT];
+#pragma unroll
+    for (int r = 0; r < NR; ++r)
+#pragma unroll
+        for (int a = 0; a < NT; ++a) HW[r][a] = cmul(H[r][a], mk<double>(w, 0.0));
+#pragma unroll
+    for (int set = 0; set < 2; ++set) {
+        double2 G[NT][NR];
+        const bool fok = set == 0 ? blast_filter<NT, NR>(Hest, p.filter_nv, G) : blast_filter<NT, NR>(H, p.filter_nv, G);
+        ok = ok && fok;
+        cx<T>* out = rec + set * kPilotSet;
+#pragma unroll
+        for (int i = 0; i < kPilotMax; ++i)
+#pragma unroll
+            for (int l = 0; l < kPilotMax; ++l) {
+                double2 acc = zero, g = zero;
+                if (i < NT && l < NT) {
+#pragma unroll
+                    for (int r = 0; r < NR; ++r) acc = cadd(acc, cmul(G[i < NT ? i : 0][r], HW[r][l < NT ? l : 0]));
+                }
+                if (i < NT && l < NR) g = G[i < NT ? i : 0][l < NR ? l : 0];
+                out[i * kPilotMax + l] = mk<T>((T)acc.x, (T)acc.y);
+                out[kPilotMax * kPilotMax + i * kPilotMax + l] = mk<T>((T)g.x, (T)g.y);
+            }
+    }
+    rec[2 * kPilotSet] = mk<T>(ok ? (T)1 : (T)0, (T)0);
+}
+
+// what the decisions of a column need, fixed for the launch
+template <typename T> struct PilotWalk {
+    const ModemParams<T>& mp;
+    const cx<T>* s_table;
+    const float4* s_tab4;
+    const unsigned long long* s_grid;
+    QamPack qp;
+    uint32_t layer_mask;
+    bool lockstep, packed;
+    int nt, nr;
+};
+
+// the decisions of one column and their errors: the Blast branch of k_mimo_flat_link's column
+template <typename T>
+__device__ __forceinline__ void pilot_decide(const PilotWalk<T>& w, const cx<T> (&est)[kPilotMax], const int (&tx)[kPilotMax],
+                                             unsigned& se, unsigned& be) {
+    if constexpr (sizeof(T) == 4) {
+        if (w.packed) {   // the column's decisions in one packed level-domain slice (qam_pack.hpp)
+            const f4q er = {est[0].x, est[1].x, est[2].x, est[3].x}, ei = {est[0].y, est[1].y, est[2].y, est[3].y};
+            const uint32_t sent = (uint32_t)tx[0] | ((uint32_t)tx[1] << 8) | ((uint32_t)tx[2] << 16) | ((uint32_t)tx[3] << 24);
+            qam_count4((qam_levels4(er, ei, w.qp) ^ labels_to_levels(sent, w.qp)) & w.layer_mask, w.qp, se, be);
+            return;
+        }
+    }
+    int dec[kPilotMax];
+    bool done = false;
+    if constexpr (sizeof(T) == 4) {
+        if (w.lockstep) {   // the layers searched in lockstep; unused layers carry est = 0 and are not counted
+            if (w.mp.M <= 8) demod_multi_cert(w.mp, est, dec, [&](int (&d_)[kPilotMax]) { demod_mindist_multi<kPilotMax>(w.s_tab4, w.mp.M, est, d_); });
+            else demod_multi_cert(w.mp, est, dec, [&](int (&d_)[kPilotMax]) { demod_grid4_multi<kPilotMax>(w.s_tab4, w.s_grid, w.mp.grid, w.mp.M, est, d_); });
+            done = true;
+        }
+    }
+    if (!done) {
+#pragma unroll
+        for (int l = 0; l < kPilotMax; ++l) dec[l] = l < w.nt ? demod_one(w.mp, w.s_table, w.s_grid, est[l]) : 0;
+    }
+#pragma unroll
+    for (int l = 0; l < kPilotMax; ++l)
+        if (l < w.nt) {
+            const unsigned xr = (unsigned)(tx[l] ^ dec[l]);
+            se += (xr != 0u);
+            be += __popc(xr);
+        }
+}
+
+// COLS symbol columns of one lane through both filters: est = A d + G n per filter, in the association of k_mimo_flat_link; an
+// entry of the record (the wavefront's LDS copy) is read once and serves every column
+template <typename T, int COLS>
+__device__ __forceinline__ void pilot_columns(const PilotWalk<T>& w, const cx<T>* s_rec, const int (&tx)[COLS][kPilotMax],
+                                              const cx<T> (&nz)[COLS][kPilotMax], unsigned (&se)[2], unsigned (&be)[2]) {
+    cx<T> d[COLS][kPilotMax];
+#pragma unroll
+    for (int c = 0; c < COLS; ++c)
+#pragma unroll
+        for (int l = 0; l < kPilotMax; ++l) d[c][l] = l < w.nt ? w.s_table[tx[c][l]] : mk<T>(0, 0);
+#pragma unroll
+    for (int set = 0; set < 2; ++set) {
+        const cx<T>* A = s_rec + set * kPilotSet;
+        const cx<T>* G = A + kPilotMax * kPilotMax;
+        cx<T> est[COLS][kPilotMax];
+#pragma unroll
+        for (int l = 0; l < kPilotMax; ++l) {
+#pragma unroll
+            for (int c = 0; c < COLS; ++c) est[c][l] = mk<T>(0, 0);
+            if (l < w.nt) {
+#pragma unroll
+                for (int k = 0; k < kPilotMax; ++k) {
+                    if (k < w.nt) {
+                        const cx<T> a = A[l * kPilotMax + k];
+#pragma unroll
+                        for (int c = 0; c < COLS; ++c) est[c][l] = cfma4(a, d[c][k], est[c][l]);
+                    }
+                    if (k < w.nr) {
+                        const cx<T> g = G[l * kPilotMax + k];
+#pragma unroll
+                        for (int c = 0; c < COLS; ++c) est[c][l] = cfma4(g, nz[c][k], est[c][l]);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < COLS; ++c) pilot_decide<T>(w, est[c], tx[c], se[set], be[set]);
+    }
+}
+
+// wavefronts per SIMD the walk's registers are bounded for: complex64 three (at the four of k_mimo_flat_link the two sets of
+// estimates spill 17 registers), complex128 two
+template <typename T> constexpr int pilot_walk_waves() { return sizeof(T) == 4 ? 3 : 2; }
+
+template <typename T>
+__global__ __launch_bounds__(256, pilot_walk_waves<T>()) void k_mimo_pilot_link(
+    ModemParams<T> mp, int nt, int nr, int n_symbols, double noise_var, uint64_t seed, uint64_t first, uint64_t count,
+    int per_wave, const cx<T>* __restrict__ recs, mcle_counters* counters, uint32_t* __restrict__ sym_est,
+    uint32_t* __restrict__ bit_est, uint32_t* __restrict__ sym_perf, uint32_t* __restrict__ bit_perf) {
+    __shared__ cx<T> s_table[256];
+    __shared__ float4 s_tab4[sizeof(T) == 4 ? 256 : 1];     // {re, im, |c|^2 / 2, 0}: the lockstep searches of modem.hpp
+    extern __shared__ unsigned long long s_grid[];          // [G*G] candidate grid (min-distance demodulation)
+    __shared__ double s_bm[sizeof(T) == 8 ? kBmLdsDoubles : 1];   // complex128 Box-Muller tables (bm_f64.hpp)
+    __shared__ cx<T> s_rec_all[4][kPilotRec + 1];           // each wavefront's current record
+    __shared__ WgTotals totals_all[2][4];                   // [estimated | perfect CSI][wavefront]
+    if constexpr (sizeof(T) == 8) bm_tables_to_lds(s_bm, (int)threadIdx.x, (int)blockDim.x);
+    load_table(mp, s_table);
+    load_grid(mp, s_grid);
+    if constexpr (sizeof(T) == 4)
+        for (int m = threadIdx.x; m < mp.M; m += blockDim.x) {
+            const float2 c = mp.g_table[m];
+            s_tab4[m] = make_float4(c.x, c.y, 0.5f * (c.x * c.x + c.y * c.y), 0.f);
+        }
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const T sigma = (T)sqrt(noise_var);
+    const uint32_t mask = (uint32_t)(mp.M - 1);
+    PilotWalk<T> w{mp, s_table, s_tab4, s_grid, QamPack{}, nt >= 4 ? 0xFFFFFFFFu : ((1u << (8 * nt)) - 1u),
+                   sizeof(T) == 4 && mp.method == MCLE_DEMOD_MINDIST && (mp.M <= 8 || mp.grid.G > 0),
+                   sizeof(T) == 4 && mp.method == MCLE_DEMOD_QAM_SLICER, nt, nr};
+    if constexpr (sizeof(T) == 4) {
+        if (w.packed) w.qp = qam_pack(mp);
+    }
+    cx<T>* s_rec = s_rec_all[wv];
+    if (lane == 0) {
+        wg_zero(totals_all[0][wv]);
+        wg_zero(totals_all[1][wv]);
+    }
+    __syncthreads();
+    const uint64_t n_chunks = (count + per_wave - 1) / per_wave;
+    for (uint64_t ch = (uint64_t)blockIdx.x * 4 + wv; ch < n_chunks; ch += (uint64_t)gridDim.x * 4) {
+        const uint64_t r_end = (ch + 1) * per_wave < count ? (ch + 1) * per_wave : count;
+        for (uint64_t rl = ch * per_wave; rl < r_end; ++rl) {
+            const Rng rng(seed, first + rl);
+            const cx<T>* rec = recs + rl * kPilotRec;
+            for (int i = lane; i < kPilotRec; i += 64) s_rec[i] = rec[i];
+            wave_lds_sync();
+            unsigned se[2] = {0u, 0u}, be[2] = {0u, 0u};
+            if ((n_symbols & 1) == 0) {
+                for (int t0 = 0; t0 < n_symbols; t0 += kPairCols) {
+                    // (the record is read where it is used, every pass: hoisted out of the loop its 128 complex values would
+                    //  not fit the registers)
+                    asm volatile("" ::: "memory");
+                    const int t = t0 + 2 * lane;
+                    if (t < n_symbols) {
+                        int tx[2][kPilotMax];
+#pragma unroll
+                        for (int l = 0; l < kPilotMax; ++l) tx[0][l] = tx[1][l] = 0;
+                        // Fortran order: the 2 nt bytes of columns t, t + 1 are consecutive (<= 8 bytes, in one block unless
+                        // nt == 3)
+                        const uint32_t q = (uint32_t)t * (uint32_t)nt;
+                        const Words4 b0 = rng.block(STREAM_DATA, q >> 4);
+                        Words4 b1 = b0;
+                        if ((q & 15u) + 2u * (uint32_t)nt > 16u) b1 = rng.block(STREAM_DATA, (q >> 4) + 1u);
+#pragma unroll
+                        for (int e = 0; e < 2 * kPilotMax; ++e)
+                            if (e < 2 * nt) {
+                                const uint32_t pos = (q & 15u) + (uint32_t)e;          // 0 .. 31
+                                const uint32_t wi = (pos >> 2) & 3u;
+                                const uint32_t lo = wi == 0 ? b0.w[0] : (wi == 1 ? b0.w[1] : (wi == 2 ? b0.w[2] : b0.w[3]));
+                                const uint32_t hi = wi == 0 ? b1.w[0] : (wi == 1 ? b1.w[1] : (wi == 2 ? b1.w[2] : b1.w[3]));
+                                const int v = (int)(((pos < 16u ? lo : hi) >> ((pos & 3u) * 8u)) & mask);
+                                // e = column * nt + layer
+#pragma unroll
+                                for (int l = 0; l < kPilotMax; ++l) {
+                                    if (e == l) tx[0][l] = v;
+                                    if (e == nt + l) tx[1][l] = v;
+                                }
+                            }
+                        cx<T> nz[2][kPilotMax];
+#pragma unroll
+                        for (int r = 0; r < kPilotMax; ++r) {
+                            nz[0][r] = nz[1][r] = mk<T>(0, 0);
+                            if (r < nr)
+                                cn_pair_lds(rng, STREAM_NOISE, ((uint32_t)r * (uint32_t)n_symbols + (uint32_t)t) >> 1, sigma,
+                                            nz[0][r], nz[1][r], s_bm);
+                        }
+                        pilot_columns<T, 2>(w, s_rec, tx, nz, se, be);
+                    }
+                }
+            } else {
+                for (int t = lane; t < n_symbols; t += 64) {
+                    asm volatile("" ::: "memory");
+                    int tx[1][kPilotMax];
+                    cx<T> nz[1][kPilotMax];
+#pragma unroll
+                    for (int l = 0; l < kPilotMax; ++l) tx[0][l] = l < nt ? (int)symbol_at(rng, (uint64_t)t * nt + l, mask) : 0;
+#pragma unroll
+                    for (int r = 0; r < kPilotMax; ++r)
+                        nz[0][r] = r < nr ? cn_sample<T>(rng, STREAM_NOISE, (uint64_t)r * n_symbols + t, sigma) : mk<T>(0, 0);
+                    pilot_columns<T, 1>(w, s_rec, tx, nz, se, be);
+                }
+            }
+            const bool skipped = s_rec[2 * kPilotSet].x == (T)0;
+#pragma unroll
+            for (int set = 0; set < 2; ++set) {
+                const unsigned s_sum = wave_sum_u32(se[set]), b_sum = wave_sum_u32(be[set]);
+                if (lane == 0)
+                    wg_account(totals_all[set][wv], s_sum, b_sum, skipped, rl, set == 0 ? sym_est : sym_perf,
+                               set == 0 ? bit_est : bit_perf);
+            }
+            wave_lds_sync();                    // the record's readers, before the next one overwrites it
+        }
+    }
+    // one flush phase per workgroup: block 0, then block 1
+    const unsigned long long n_sym = (unsigned long long)nt * n_symbols;
+    wg_flush_waves<4>(totals_all[0], counters, n_sym, n_sym * mp.bits);
+    wg_flush_waves<4>(totals_all[1], counters ? counters + 1 : nullptr, n_sym, n_sym * mp.bits);
+}
+
+typedef std::complex<double> pilot_zc;
+
+// (s s^H)^-1 of the fixed pilots s [nt][P] by Gauss-Jordan with partial pivoting, complex128; false: numerically singular
+static bool pilot_gram_inverse(const pilot_zc* s, int nt, int P, double2* ginv) {
+    pilot_zc g[kPilotMax][kPilotMax], inv[kPilotMax][kPilotMax];
+    double tr = 0.0;
+    for (int a = 0; a < nt; ++a)
+        for (int b = 0; b < nt; ++b) {
+            pilot_zc acc(0.0, 0.0);
+            for (int p = 0; p < P; ++p) acc += s[a * P + p] * std::conj(s[b * P + p]);
+            g[a][b] = acc;
+            inv[a][b] = a == b ? pilot_zc(1.0, 0.0) : pilot_zc(0.0, 0.0);
+            if (a == b) tr += acc.real();
+        }
+    if (!std::isfinite(tr) || !(tr > 0.0)) return false;
+    for (int k = 0; k < nt; ++k) {
+        int piv = k;
+        for (int i = k + 1; i < nt; ++i)
+            if (std::abs(g[i][k]) > std::abs(g[piv][k])) piv = i;
+        if (!(std::abs(g[piv][k]) > kPilotPivotFloor * tr)) return false;
+        for (int j = 0; j < nt; ++j) {
+            std::swap(g[k][j], g[piv][j]);
+            std::swap(inv[k][j], inv[piv][j]);
+        }
+        const pilot_zc d = 1.0 / g[k][k];
+        for (int j = 0; j < nt; ++j) {
+            g[k][j] *= d;
+            inv[k][j] *= d;
+        }
+        for (int i = 0; i < nt; ++i) {
+            if (i == k) continue;
+            const pilot_zc f = g[i][k];
+            for (int j = 0; j < nt; ++j) {
+                g[i][j] -= f * g[k][j];
+                inv[i][j] -= f * inv[k][j];
+            }
+        }
+    }
+    for (int a = 0; a < nt; ++a)
+        for (int b = 0; b < nt; ++b) ginv[a * kPilotMax + b] = make_double2(inv[a][b].real(), inv[a][b].imag());
+    return true;
+}
+
+template <typename T, int NT, int NR>
+static void launch_pilot_setup(mcle_ctx* ctx, const PilotSetup& p, const double* d_pilots, const double* d_L, const double* d_B,
+                               uint64_t seed, uint64_t first, uint64_t m, void* recs, double* d_err, double* d_pow) {
+    hipLaunchKernelGGL((k_mimo_pilot_setup<T, NT, NR>), dim3((unsigned)((m + 63) / 64)), dim3(64), 0, ctx->stream, p,
+                       (const double2*)d_pilots, (const double2*)d_L, (const double2*)d_B, seed, first, m, (cx<T>*)recs, d_err,
+                       d_pow);
+}
+
+template <typename T>
+static int run_mimo_pilot_link(mcle_ctx* ctx, const mcle_mimo_pilot_cfg* cfg, const PilotSetup& p, uint64_t seed, uint64_t first,
+                               uint64_t count, const double* d_pilots, const double* d_L, const double* d_B,
+                               mcle_counters* d_counters, uint32_t* d_sym_err, uint32_t* d_bit_err, double* d_err,
+                               double* d_pow) {
+    const int nt = cfg->nt, nr = cfg->nr;
+    const ModemParams<T> mp = pipe_modem<T>(ctx, cfg->demod_method);
+    const size_t lds = (size_t)mp.grid.G * mp.grid.G * sizeof(unsigned long long);
+    const int per_wave = 16;
+    // records of a slice of realizations, then their walk: at most 512 MiB of records per pair of launches, less on a crowded
+    // device (scratch_upto)
+    const size_t one = (size_t)kPilotRec * sizeof(cx<T>);
+    uint64_t slice = ((size_t)512 << 20) / one;
+    if (slice > count) slice = count;
+    void* recs = nullptr;
+    size_t got = 0;
+    int rc;
+    if ((rc = ctx->scratch_upto((size_t)slice * one, (size_t)(slice < 64 ? slice : 64) * one, &recs, &got))) return rc;
+    if (got / one < slice) slice = got / one;
+    // A unit is four chunks = 64 realizations of 2 nt (nt + nr) n_symbols complex multiply-adds each; the workgroup's one flush
+    // phase is twelve atomics (pipe_common.hpp: flush_min_units, the estimate of pipeline_ia_general.hip)
+    const uint64_t min_units = flush_min_units(2, 1u << 14, 2ull * nt * (nt + nr) * (uint64_t)cfg->n_symbols);
+    const uint64_t resident = (uint64_t)ctx->n_cu * pilot_walk_waves<T>();               // workgroups of four wavefronts
+    for (uint64_t off = 0; off < count; off += slice) {
+        const uint64_t m = count - off < slice ? count - off : slice;
+        double* e_out = d_err ? d_err + off : nullptr;
+        double* p_out = d_pow ? d_pow + off : nullptr;
+#define MCLE_PS(NT_, NR_) \
+    if (nt == NT_ && nr == NR_) launch_pilot_setup<T, NT_, NR_>(ctx, p, d_pilots, d_L, d_B, seed, first + off, m, recs, e_out, p_out);
+        MCLE_PS(1, 1) MCLE_PS(1, 2) MCLE_PS(1, 3) MCLE_PS(1, 4) MCLE_PS(2, 2) MCLE_PS(2, 3) MCLE_PS(2, 4) MCLE_PS(3, 3)
+        MCLE_PS(3, 4) MCLE_PS(4, 4)
+#undef MCLE_PS
+        MCLE_LAUNCH_CHECK();
+        const uint64_t chunks = (m + per_wave - 1) / per_wave;
+        const unsigned grid = (unsigned)oversubscribed_grid(ctx, resident, (chunks + 3) / 4, min_units);
+        hipLaunchKernelGGL(k_mimo_pilot_link<T>, dim3(grid), dim3(256), lds, ctx->stream, mp, nt, nr, cfg->n_symbols,
+                           cfg->noise_var, seed, first + off, m, per_wave, (const cx<T>*)recs, d_counters,
+                           d_sym_err ? d_sym_err + off : nullptr, d_bit_err ? d_bit_err + off : nullptr,
+                           d_sym_err ? d_sym_err + count + off : nullptr, d_bit_err ? d_bit_err + count + off : nullptr);
+        MCLE_LAUNCH_CHECK();
+    }
+    ctx->set_kernel("mimo_pilot_link %s %s", sizeof(T) == 8 ? "f64" : "f32", cfg->estimator ? "mmse" : "ls");
+    return MCLE_OK;
+}
+
+}  // namespace mcle
+
+using namespace mcle;
+
+extern "C" int mcle_run_mimo_pilot_link(mcle_ctx* ctx, int dtype, const mcle_mimo_pilot_cfg* cfg, uint64_t seed, uint64_t first,
+                                        uint64_t count, const double* d_pilots, const double* d_chan_factor,
+                                        const double* d_mmse_matrix, mcle_counters* d_counters, uint32_t* d_sym_err,
+                                        uint32_t* d_bit_err, double* d_err, double* d_pow) {
+    if (ctx) ctx->last_kernel[0] = 0;
+    int rc = check_pipe(ctx, dtype, cfg ? cfg->demod_method : 0, cfg);
+    if (rc) return rc;
+    const int nt = cfg->nt, nr = cfg->nr, P = cfg->n_pilots;
+    MCLE_REQUIRE(nt >= 1 && nt <= nr && nr <= kPilotMax, "antenna counts must satisfy 1 <= nt <= nr <= %d (got nt %d, nr %d)", kPilotMax,
+                 nt, nr);
+    MCLE_REQUIRE(P >= nt && P <= kPilotMaxPilots, "n_pilots must be in [nt, %d] (got %d pilots, nt %d)", kPilotMaxPilots, P, nt);
+    MCLE_REQUIRE(cfg->n_symbols >= 1, "n_symbols must be positive");
+    MCLE_REQUIRE(cfg->estimator == 0 || cfg->estimator == 1, "estimator must be 0 (LS) or 1 (MMSE) (got %d)", cfg->estimator);
+    MCLE_REQUIRE(cfg->random_pilots == 0 || cfg->random_pilots == 1, "random_pilots must be 0 or 1 (got %d)", cfg->random_pilots);
+    MCLE_REQUIRE(cfg->mmse_filter == 0 || cfg->mmse_filter == 1, "mmse_filter must be 0 or 1 (got %d)", cfg->mmse_filter);
+    MCLE_REQUIRE(std::isfinite(cfg->noise_var) && cfg->noise_var >= 0.0, "Noise variance must be a non-negative value.");
+    MCLE_REQUIRE(std::isfinite(cfg->pilot_power) && cfg->pilot_power > 0.0, "pilot_power must be finite and positive");
+    MCLE_REQUIRE(std::isfinite(cfg->alpha), "alpha must be finite");
+    MCLE_REQUIRE(cfg->random_pilots || d_pilots != nullptr, "null d_pilots with random_pilots = 0");
+    MCLE_REQUIRE(cfg->estimator == 0 || nt == 1, "the MMSE estimator needs nt = 1 (got %d)", nt);
+    MCLE_REQUIRE(cfg->estimator == 0 || d_mmse_matrix != nullptr, "the MMSE estimator needs d_mmse_matrix (from a covariance)");
+    MCLE_REQUIRE((uint64_t)nr * (uint64_t)cfg->n_symbols <= 0x7fffffffull, "n_symbols too large: draw positions are 32-bit");
+    MCLE_REQUIRE(count <= 0x7fffffffull, "at most 2^31-1 realizations per call");
+    if (count == 0) return MCLE_OK;
+    MCLE_REQUIRE(d_counters != nullptr, "null d_counters");
+    if ((rc = ctx->bind())) return rc;
+    PilotSetup p{};
+    p.P = P, p.half = (P + 1) / 2;
+    p.random_pilots = cfg->random_pilots, p.mmse_est = cfg->estimator, p.gram_ok = 1;
+    p.amp = std::sqrt(cfg->pilot_power), p.sigma = std::sqrt(cfg->noise_var), p.alpha = cfg->alpha;
+    p.filter_nv = cfg->mmse_filter ? cfg->noise_var : 0.0;
+    if (!cfg->random_pilots) {
+        // the fixed block's inverse Gram matrix, once, on the host
+        std::vector<pilot_zc> s((size_t)nt * P);
+        MCLE_HIP(hipMemcpyAsync(s.data(), d_pilots, s.size() * sizeof(pilot_zc), hipMemcpyDeviceToHost, ctx->stream));
+        MCLE_HIP(hipStreamSynchronize(ctx->stream));
+        p.gram_ok = pilot_gram_inverse(s.data(), nt, P, p.ginv) ? 1 : 0;
+    }
+    return dtype == MCLE_F32 ? run_mimo_pilot_link<float>(ctx, cfg, p, seed, first, count, d_pilots, d_chan_factor, d_mmse_matrix,
+                                                          d_counters, d_sym_err, d_bit_err, d_err, d_pow)
+                             : run_mimo_pilot_link<double>(ctx, cfg, p, seed, first, count, d_pilots, d_chan_factor, d_mmse_matrix,
+                                                           d_counters, d_sym_err, d_bit_err, d_err, d_pow);
+}

@@ -1493,6 +1493,54 @@ class Engine:
         res = {"n_realizations": int(count), "err_ls": tot[0], "err_mmse": tot[1], "pow": tot[2]}
         return (res, arrs[0], arrs[1], arrs[2]) if per_realization else res
 
+    def run_mimo_pilot_link(self, nt, nr, n_pilots, n_symbols, noise_var, seed, first, count, pilot_power=1.0, alpha=1.0,
+                            pilots=None, chan_factor=None, cov=None, estimator="ls", mmse=False, method=DEMOD_MINDIST,
+                            dtype=None, per_realization=False):
+        """The flat Blast link with pilot-estimated and with perfect channel state on the same draws
+        (mcle_run_mimo_pilot_link): per realization H = alpha chan_factor W, a block of n_pilots pilots (drawn with power
+        pilot_power, or `pilots` [nt, n_pilots]), the LS estimate -- or with estimator='mmse' (nt = 1) the MMSE one for the
+        covariance `cov` [nr, nr], turned here into B = (noise_var I + n_pilots cov)^-1 cov --, the Blast filter from the
+        estimate and from H (mmse=True: set_noise_var(noise_var)), n_symbols per layer.  Returns (counters with estimated
+        CSI, counters with perfect CSI); with per_realization=True also sym_err [2, count], bit_err [2, count] (row 0
+        estimated, row 1 perfect; 0xFFFFFFFF marks a skipped realization), err [count] = |H^ - H|_F^2, pow [count] = |H|_F^2."""
+        dt = self._dt(dtype)
+        nt, nr, P, count = int(nt), int(nr), int(n_pilots), int(count)
+        if estimator not in _lib.PILOT_ESTIMATORS:
+            raise ValueError("estimator must be 'ls' or 'mmse' (got %r)" % (estimator,))
+        cfg = _lib.MimoPilotCfg(nt, nr, P, int(n_symbols), int(method), _lib.PILOT_ESTIMATORS[estimator],
+                                1 if pilots is None else 0, 1 if mmse else 0, float(noise_var), float(pilot_power),
+                                float(alpha))
+        d_p = d_L = d_B = None
+        if pilots is not None:
+            s = np.asarray(pilots, dtype=np.complex128)
+            if s.shape != (nt, P):
+                raise ValueError("pilots must be [nt, n_pilots] = [%d, %d] (got %s)" % (nt, P, s.shape))
+            d_p = self.to_device(s, np.complex128)
+        if chan_factor is not None:
+            d_L = self.to_device(self._host_c128(chan_factor, nr, "chan_factor")[0], np.complex128)
+        if estimator == "mmse" and cov is not None:          # (nt > 1 or no covariance: the library refuses)
+            C = self._host_c128(cov, nr, "cov")[0]
+            M = float(noise_var) * np.eye(nr) + P * C
+            if not (np.all(np.isfinite(M)) and np.linalg.matrix_rank(M) == nr):
+                raise ValueError("noise_var * I + n_pilots * cov is singular")
+            d_B = self.to_device(np.linalg.solve(M, C), np.complex128)
+        cnt = self.zeros(2, np.dtype((np.void, ctypes.sizeof(Counters))))
+        se = be = err = pw = None
+        if per_realization:
+            se, be = self.empty((2, count), np.uint32), self.empty((2, count), np.uint32)
+            err, pw = self.empty(count, np.float64), self.empty(count, np.float64)
+        self._raise_value(self.lib.mcle_run_mimo_pilot_link(
+            self.ctx, dt, byref(cfg), int(seed), int(first), count, d_p.ptr if d_p is not None else None,
+            d_L.ptr if d_L is not None else None, d_B.ptr if d_B is not None else None, cnt.ptr,
+            se.ptr if per_realization else None, be.ptr if per_realization else None,
+            err.ptr if per_realization else None, pw.ptr if per_realization else None))
+        raw = cnt.get().tobytes()
+        size = ctypes.sizeof(Counters)
+        res = tuple(Counters.from_buffer_copy(raw[i * size:(i + 1) * size]).as_dict() for i in range(2))
+        if per_realization:
+            return res + (se.get(), be.get(), err.get(), pw.get())
+        return res
+
     # ---- Grassmannian codebooks (csrc/kernels_codebook.hip) -------------------------------------------
     def chordal_min_dist(self, codebooks, dtype=None, full=False):
         """Squared chordal distances of codebooks [n, K, Nt, Ns] (or one [K, Nt, Ns]) (mcle_chordal_min_dist): returns

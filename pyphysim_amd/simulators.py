@@ -567,6 +567,88 @@ class PilotEstimationSimulator(BatchedSimulationRunner):
         return res
 
 
+class PilotMimoSimulator(_LinkSimulator):
+    """What imperfect channel state costs the flat Blast link (MimoSimulator's 'blast'; the estimators of
+    channel_estimation/estimators.py, Fodor et al. 2014, in front of mimo.Blast): per realization a channel h = alpha L w, a block
+    of `num_pilots` pilots of power `pilot_power` (random phases when random_pilots, else the first rows of a DFT matrix), the LS
+    estimate -- or with estimator='mmse' and a covariance `C` (`Nr` x `Nr`, Nt = 1: L = cholesky(C), the estimator is handed
+    alpha^2 C) the MMSE one --, and `NSymbs` symbols per layer decoded with the Blast filter of the estimate and with that of the
+    true channel, on the same data and the same noise.  Pilots and data see the same noise power 1 / SNR; `mmse=True` is
+    Blast.set_noise_var.  One call into libmcle per batch (Engine.run_mimo_pilot_link).
+
+    Results: 'ber', 'ser' (and the counts behind them) with estimated CSI; 'ber_perfect_csi', 'ser_perfect_csi' with the true
+    channel; 'mse' = RATIO(sum |h^ - h|^2, alpha^2 n) for LS and RATIO(sum |h^ - h|^2, n) for MMSE, PilotEstimationSimulator's
+    'mse_ls' / 'mse_mmse'; 'channel_power' = RATIO(sum |h|^2, n); 'elapsed_time'.  The sums of the errors are kept as exact integer
+    limbs, so the results do not depend on batch_size or on the number of ranks."""
+
+    _SUMS = ("err", "pow")
+    _PERFECT = ("sym_errors_perfect", "sym_errors_sq_perfect", "bit_errors_perfect", "bit_errors_sq_perfect")
+    EXTRA_INT_KEYS = _PERFECT
+    EXTRA_KEYS = _PERFECT + tuple("%s_l%d" % (k, i) for k in _SUMS for i in range(3)) + tuple(k + "_sq" for k in _SUMS)
+
+    def __init__(self, SNR, Nr=2, Nt=2, num_pilots=4, NSymbs=200, modulator="qam", M=16, pilot_power=1.0, alpha=1.0, C=None,
+                 estimator="ls", random_pilots=True, mmse=False, **kw):
+        kw.setdefault("dtype", "f64")
+        super().__init__(SNR, modulator, M, **kw)
+        if estimator not in _lib.PILOT_ESTIMATORS:
+            raise ValueError("estimator must be 'ls' or 'mmse' (got %r)" % (estimator,))
+        self._L = self._cov = None
+        if C is not None:
+            C = np.asarray(C, dtype=np.complex128)
+            if C.shape != (int(Nr), int(Nr)):
+                raise ValueError("C must be [Nr, Nr] = [%d, %d]" % (Nr, Nr))
+            self._L, self._cov = np.linalg.cholesky(C), float(alpha) ** 2 * C
+        if estimator == "mmse":
+            if int(Nt) != 1:
+                raise ValueError("the MMSE estimator needs Nt = 1 (it is SIMO)")
+            if C is None:
+                raise ValueError("the MMSE estimator needs a covariance C")
+        self._pilots = None
+        if not random_pilots:
+            t, p = np.arange(int(Nt))[:, None], np.arange(int(num_pilots))[None, :]
+            self._pilots = np.sqrt(float(pilot_power)) * np.exp(-2j * np.pi * t * p / int(num_pilots))
+        for k, v in (("Nr", int(Nr)), ("Nt", int(Nt)), ("num_pilots", int(num_pilots)), ("NSymbs", int(NSymbs)),
+                     ("pilot_power", float(pilot_power)), ("alpha", float(alpha)), ("estimator", estimator),
+                     ("random_pilots", bool(random_pilots)), ("mmse", bool(mmse))):
+            self.params.add(k, v)
+
+    def _launch(self, current_parameters, first_rep, count, per_realization):
+        p = current_parameters
+        eng = self._bind()
+        c_est, c_perf, se, be, err, pw = eng.run_mimo_pilot_link(
+            p["Nt"], p["Nr"], p["num_pilots"], p["NSymbs"], self._noise_var(p), self._seed_for(p), first_rep, count,
+            pilot_power=p["pilot_power"], alpha=p["alpha"], pilots=self._pilots, chan_factor=self._L,
+            cov=self._cov if p["estimator"] == "mmse" else None, estimator=p["estimator"], mmse=p["mmse"],
+            method=self.demod_method, dtype=self.dtype, per_realization=True)
+        c = dict(c_est)
+        for k in ("sym_errors", "sym_errors_sq", "bit_errors", "bit_errors_sq"):
+            c[k + "_perfect"] = c_perf[k]
+        good = se[0] != 0xFFFFFFFF                   # (a skipped realization's err / pow are unspecified)
+        for key, arr in zip(self._SUMS, (err[good], pw[good])):
+            for i, v in enumerate(_exact_limbs(arr)):
+                c["%s_l%d" % (key, i)] = v
+            c[key + "_sq"] = float(np.square(arr).sum())
+        return c, se[0], be[0]
+
+    def _run_batch(self, current_parameters, first_rep, count):
+        return self._launch(current_parameters, first_rep, count, False)[0]
+
+    def _results_from_counters(self, current_parameters, c):
+        from .simulations import Result
+        res = super()._results_from_counters(current_parameters, c)
+        n = c["n_realizations"]
+        res.add_result(Result.from_counters("ber_perfect_csi", Result.RATIOTYPE, int(c.get("bit_errors_perfect", 0)),
+                                            int(c.get("bit_errors_sq_perfect", 0)), c["n_bits"], n))
+        res.add_result(Result.from_counters("ser_perfect_csi", Result.RATIOTYPE, int(c.get("sym_errors_perfect", 0)),
+                                            int(c.get("sym_errors_sq_perfect", 0)), c["n_symbols"], n))
+        m = max(int(n), 1)
+        norm = 1.0 if current_parameters["estimator"] == "mmse" else current_parameters["alpha"] ** 2
+        err, pw = _from_limbs(c, "err"), _from_limbs(c, "pow")
+        res.add_result(Result.from_batch("mse", Result.RATIOTYPE, err, norm * m, err / norm, float(c.get("err_sq", 0.0)) / norm ** 2, m))
+        res.add_result(Result.from_batch("channel_power", Result.RATIOTYPE, pw, float(m), pw, float(c.get("pow_sq", 0.0)), m))
+        return res
+
+
 class CompSimulator(BatchedSimulationRunner):
     """CoMP with an external interferer and stream reduction (the reference's apps/comp_BD/simulate_comp.py and its script
     form simulate_comp_with_ext_int_simple.py): `K` cells of `Nr` x `Nr` antennas precode jointly by block diagonalisation
