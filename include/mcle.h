@@ -602,6 +602,29 @@ int mcle_run_mimo_flat(mcle_ctx* ctx, int dtype, const mcle_mimo_flat_cfg* cfg, 
                        uint64_t first, uint64_t count, mcle_counters* d_counters,
                        uint32_t* d_sym_err, uint32_t* d_bit_err);
 
+/* The flat Blast link of mcle_run_mimo_flat(MCLE_MIMO_BLAST) for large arrays (csrc/pipeline_mimo_large.hip; nt = 1 is mimo.MRC): the
+ * same link, draws (CHAN sample r nt + a = H[r][a], DATA symbol t nt + a, NOISE sample r n_symbols + t), counters, n_skipped and
+ * 0xFFFFFFFF mark of a realization whose Gram matrix is not positive definite, so for shapes up to 4 x 4 the two entry points run
+ * the same realizations; mcle_run_mimo_flat keeps its 4 x 4 envelope.  est = A x + G n runs on the matrix cores
+ * (v_mfma_f64_16x16x4_f64 / v_mfma_f32_16x16x4_f32); the filter is always built in f64.
+ * Envelope: 1 <= nt <= 8, nt <= nr <= 16, n_symbols >= 1 with nr * n_symbols <= 2^31 - 1 (draw positions are 32-bit),
+ * noise_var >= 0 and finite, mmse 0 (zero forcing) or 1 (set_noise_var(noise_var)), reserved 0, count <= 2^31 - 1, either
+ * arithmetic, every demodulator of mcle_run_mimo_flat.  Anything else: MCLE_E_INVAL with a message, nothing touched.
+ * Device memory: the context's scratch buffer holds the records of one launch slice, 512 bytes per K-step and realization in
+ * complex128, 2 (ceil(nt / 4) + ceil(nr / 4)) K-steps (6 KiB at 8 x 16), half of that in complex64, at most 128 MiB in all.
+ * mcle_ctx_last_kernel: "mimo_large_link f64|f32 <nr>x<nt> s<K-steps>". */
+typedef struct mcle_mimo_large_cfg {
+    int32_t nt, nr;
+    int32_t n_symbols;                  /* NSymbs per transmit antenna */
+    int32_t demod_method;
+    int32_t mmse;                       /* 1 = set_noise_var(noise_var); 0 = zero forcing (the app) */
+    int32_t reserved;                   /* 0 */
+    double noise_var;
+} mcle_mimo_large_cfg;
+int mcle_run_mimo_large(mcle_ctx* ctx, int dtype, const mcle_mimo_large_cfg* cfg, uint64_t seed,
+                        uint64_t first, uint64_t count, mcle_counters* d_counters,
+                        uint32_t* d_sym_err, uint32_t* d_bit_err);
+
 /* Fused frequency-selective MIMO-OFDM (round 5: one receive antenna per wavefront, csrc/mimo_tdl_wave.hpp; the workgroup-cooperative
  * kernel of rounds 1-4 behind MCLE_OPT_MIMO_TDL_KERNEL = 1 and for square geometries outside the wavefront kernel's envelope).
  * Returns MCLE_E_UNSUPPORTED (and touches nothing) when the Doppler phase across half an OFDM symbol is beyond the kernels'

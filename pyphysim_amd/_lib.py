@@ -81,6 +81,11 @@ class MimoFlatCfg(Structure):
                 ("demod_method", c_int32), ("mmse", c_int32), ("noise_var", c_double)]
 
 
+class MimoLargeCfg(Structure):
+    _fields_ = [("nt", c_int32), ("nr", c_int32), ("n_symbols", c_int32), ("demod_method", c_int32),
+                ("mmse", c_int32), ("reserved", c_int32), ("noise_var", c_double)]
+
+
 MIMO_SCHEMES = {"blast": 0, "mrc": 1, "mrt": 2, "alamouti": 3, "svd": 4, "gmd": 5}
 
 
@@ -274,6 +279,7 @@ _PROTOS = {
     "mcle_run_ofdm_tdl": (c_int, [_P, c_int, POINTER(OfdmTdlCfg), c_uint64, c_uint64, c_uint64, _P, _P, _P]),
     "mcle_run_mimo_ofdm": (c_int, [_P, c_int, POINTER(MimoOfdmCfg), c_uint64, c_uint64, c_uint64, _P, _P, _P]),
     "mcle_run_mimo_flat": (c_int, [_P, c_int, POINTER(MimoFlatCfg), c_uint64, c_uint64, c_uint64, _P, _P, _P]),
+    "mcle_run_mimo_large": (c_int, [_P, c_int, POINTER(MimoLargeCfg), c_uint64, c_uint64, c_uint64, _P, _P, _P]),
     "mcle_run_mimo_ofdm_tdl": (c_int, [_P, c_int, POINTER(MimoOfdmTdlCfg), c_uint64, c_uint64, c_uint64, _P, _P,
                                        _P]),
     "mcle_run_ia": (c_int, [_P, c_int, POINTER(IaCfg), c_uint64, c_uint64, c_uint64, _P, _P, _P, _P, _P]),

@@ -865,6 +865,13 @@ class Engine:
                                1 if mmse else 0, float(noise_var))
         return self._run(self.lib.mcle_run_mimo_flat, cfg, seed, first, count, dtype, per_realization, counters)
 
+    def run_mimo_large(self, nt, nr, n_symbols, noise_var, seed, first, count, mmse=False, method=DEMOD_MINDIST,
+                       dtype=None, per_realization=False, counters=None):
+        """The flat Blast link of run_mimo_flat('blast') for large arrays: 1 <= nt <= 8, nt <= nr <= 16 (nt = 1 is the
+        reference's MRC), on the matrix cores; the same draws, so up to 4 x 4 the same link as run_mimo_flat."""
+        cfg = _lib.MimoLargeCfg(int(nt), int(nr), int(n_symbols), int(method), 1 if mmse else 0, 0, float(noise_var))
+        return self._run(self.lib.mcle_run_mimo_large, cfg, seed, first, count, dtype, per_realization, counters)
+
     def run_mimo_ofdm_tdl(self, nt, nr, fft_size, cp_size, num_used, n_ofdm_sym, noise_var, tap_power, tap_delay,
                           seed, first, count, Fd=10.0, Ts=1.0 / (15e3 * 1024), L=8, mmse=True, method=DEMOD_MINDIST,
                           dtype=None, per_realization=False, counters=None):

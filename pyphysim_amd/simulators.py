@@ -183,6 +183,26 @@ class MimoSimulator(_LinkSimulator):
                                  per_realization=per_realization)
 
 
+class LargeMimoSimulator(_LinkSimulator):
+    """MimoSimulator's 'blast' (apps/mimo/simulate_mimo.py with mimo.Blast; Nt = 1: mimo.MRC) for arrays beyond 4 x 4:
+    1 <= Nt <= 8, Nt <= Nr <= 16, on the matrix-core link (Engine.run_mimo_large).  Same draws as MimoSimulator, so up to
+    4 x 4 the two give the same counts in complex128.  `mmse=True` is Blast.set_noise_var(noise_var)."""
+
+    def __init__(self, SNR, Nt=8, Nr=8, NSymbs=200, modulator="qam", M=16, mmse=False, **kw):
+        super().__init__(SNR, modulator, M, **kw)
+        if not (1 <= int(Nt) <= 8 and int(Nt) <= int(Nr) <= 16):
+            raise ValueError("LargeMimoSimulator needs 1 <= Nt <= 8 and Nt <= Nr <= 16 (got Nt %d, Nr %d)" % (Nt, Nr))
+        for k, v in (("Nt", int(Nt)), ("Nr", int(Nr)), ("NSymbs", int(NSymbs)), ("mmse", bool(mmse))):
+            self.params.add(k, v)
+
+    def _launch(self, current_parameters, first_rep, count, per_realization):
+        p = current_parameters
+        eng = self._bind()
+        return eng.run_mimo_large(p["Nt"], p["Nr"], p["NSymbs"], self._noise_var(p), self._seed_for(p), first_rep, count,
+                                  mmse=p["mmse"], method=self.demod_method, dtype=self.dtype,
+                                  per_realization=per_realization)
+
+
 class BdSimulator(_LinkSimulator):
     """apps/comp_BD/simulate_comp_simple.py:22-140 (no external interference source): K cells with Nr x Nr antennas
     each transmit jointly through a block-diagonalising precoder (water-filling normalised to the strongest cell,
