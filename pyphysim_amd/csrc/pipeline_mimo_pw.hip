@@ -273,16 +273,34 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
 
     T* s_mine = s_R + j * kPwPlane;
     uint2* s_words_mine = reinterpret_cast<uint2*>(s_mine);                // [16 slots][64 lanes] word pairs of MY samples
-    uint64_t it = 0, rl_prev = 0;
+    // (the pass count of a workgroup: a launch has at most 2^20 realizations, 32 bits hold it -- one lane instead of two)
+    using Pass = std::conditional_t<kAhead, uint32_t, uint64_t>;
+    Pass it = 0;
+    uint64_t rl_prev = 0;
     cx<T> rec_next = mk<T>(0, 0);
     if (tid < kRec && blockIdx.x < count) rec_next = g_recs[(uint64_t)blockIdx.x * kRec + tid];
+    // Round 22 (default form by lane row): THE HEAD OF THE REALIZATION LOOP.  The kernel holds more scalars than it has scalar
+    // registers, and what does not fit lives in the lanes of one vector register: every reload is a v_readlane_b32, every update a
+    // v_writelane_b32, on the issue slots the kernel is bound by.  The step of the loop is read ONCE as a value (it was a pointer
+    // into the launch arguments, two lanes, and a scalar load with its wait twice per realization), and what only thread 0 needs
+    // one realization later -- where the previous realization's two counts go -- is formed inside account_prev()'s branch.
+    // (every other form reads gridDim.x where it did: their code is the witness)
+    unsigned step = 0;
+    if constexpr (kAhead) {
+        step = gridDim.x;
+        asm volatile("" : "+s"(step));
+    }
+    auto grid_step = [&]() -> unsigned {
+        if constexpr (kAhead) return step;
+        else return gridDim.x;
+    };
     __syncthreads();
-    for (uint64_t rl = blockIdx.x; rl < count; rl += gridDim.x, ++it) {
+    for (uint64_t rl = blockIdx.x; rl < count; rl += grid_step(), ++it) {
         const Rng rng(seed, first + rl);
         const int buf = (int)(it & 1);
         if (tid < kRec) {                                                   // (first read after the next workgroup barrier)
             s_rec[buf * (kRec + 1) + tid] = rec_next;
-            if (rl + gridDim.x < count) rec_next = g_recs[(rl + gridDim.x) * kRec + tid];
+            if (rl + grid_step() < count) rec_next = g_recs[(rl + grid_step()) * kRec + tid];
         }
         const cx<T>* s_H = s_rec + buf * (kRec + 1);                        // [NR][NT]
         const cx<T>* s_G = s_H + NT * NR;                                   // [NT][NR]
@@ -345,7 +363,15 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                         ts += qq[2 * i];
                         tb += qq[2 * i + 1];
                     }
-                    wg_account(totals, ts, tb, s_rec[(buf ^ 1) * (kRec + 1) + 2 * NT * NR].x != 0.0, rl_prev, sym_out, bit_out);
+                    // (kAhead: the previous realization's index from this one's INSIDE the branch -- formed at the loop head, the two
+                    //  output addresses were computed by every wavefront, parked in four lanes and read back here by thread 0 alone)
+                    uint64_t rp = rl_prev;
+                    if constexpr (kAhead) {
+                        uint64_t here = rl;
+                        asm volatile("" : "+s"(here));
+                        rp = here - step;
+                    }
+                    wg_account(totals, ts, tb, s_rec[(buf ^ 1) * (kRec + 1) + 2 * NT * NR].x != 0.0, rp, sym_out, bit_out);
                 }
             };
             if constexpr (!ROWS) {
@@ -501,6 +527,21 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                 }
             }
             // ---- receive transform: pass 2' (DIT spans 1, 4), transposition back, pass 1' (spans 16, 64) ----
+            // Round 22 (default form by lane row): the six twiddles of pass 1' go out HERE, behind the draw and in front of pass 2' --
+            // their addresses depend on the lane alone, the fetched samples of the draw are dead, and behind the transposition three
+            // of them were waited on five to eight instructions behind their issue.  (In front of the transposition's first store
+            // the whole transposition lies between issue and wait, but it is LDS traffic: eight VALU instructions.)  The same loads,
+            // the same values; the scheduling barrier keeps pass 2' behind them.
+            R16Tw64<T> tw1;                                                       // the twiddles of pass 1'
+            if constexpr (kAhead) {
+                const int g = opaque(lane) & 15;
+#pragma unroll
+                for (int m = 1; m <= 3; ++m) {
+                    tw1.a1[m - 1] = g_tw[NW * g * m];
+                    tw1.a2[m - 1] = g_tw[4 * NW * g * m];
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
             if constexpr (!(ABL & 512)) {
                 R16Tw64<T> none;
                 r16_pass<T, false, true, 0, false, true, true, false, true>(nullptr, nullptr, 0, none, nullptr, 0, v, v);
@@ -532,14 +573,15 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                 for (int u = 0; u < 16; ++u) v[u] = mk<T>(xr[u], s_mine[wbase + 17 * u]);
             }
             if constexpr (!(ABL & 512)) {
-                const int g = opaque(lane) & 15;
-                R16Tw64<T> tw;
+                if constexpr (!kAhead) {
+                    const int g = opaque(lane) & 15;
 #pragma unroll
-                for (int m = 1; m <= 3; ++m) {
-                    tw.a1[m - 1] = g_tw[NW * g * m];
-                    tw.a2[m - 1] = g_tw[4 * NW * g * m];
+                    for (int m = 1; m <= 3; ++m) {
+                        tw1.a1[m - 1] = g_tw[NW * g * m];
+                        tw1.a2[m - 1] = g_tw[4 * NW * g * m];
+                    }
                 }
-                r16_pass<T, false, true, 0, false, true, true>(nullptr, nullptr, 0, tw, nullptr, 0, v, v);
+                r16_pass<T, false, true, 0, false, true, true>(nullptr, nullptr, 0, tw1, nullptr, 0, v, v);
             }
             // ---- the exchange: Y_j[k'] of receive antenna r (lane (r, g), register u: k' = g + 16 u) -> plane j at r 272 + k', re then
             //      im; lane (r, g) of wavefront jw reads the NW partial transforms of ITS k' = g + 16 (UU jw + uu), antenna r only ----
@@ -784,8 +826,16 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                 }
             }
         }
-        se = wave_sum_u32(se);
-        be = wave_sum_u32(be);
+        // Round 22 (default form by lane row): the two totals by six v_add_u32 with DPP modifiers and one v_readlane_b32 each
+        // (walk_wave_total) -- wave_sum_u32 is twelve ds_bpermute_b32 in six dependent steps, each waited on in full, in all NW
+        // wavefronts at once right in front of B5.  32-bit unsigned sums either way: the same words, wrap-around included.
+        if constexpr (kAhead) {
+            se = walk_wave_total(se);
+            be = walk_wave_total(be);
+        } else {
+            se = wave_sum_u32(se);
+            be = wave_sum_u32(be);
+        }
         if (lane == 0) {
             s_part[buf * 32 + 2 * j] = se;
             s_part[buf * 32 + 2 * j + 1] = be;
@@ -803,6 +853,8 @@ __global__ __launch_bounds__(64 * NW, WPS) void k_run_mimo_ofdm_pw(MimoParams pp
                 ts += qq[2 * i];
                 tb += qq[2 * i + 1];
             }
+            // (kAhead: the index of the last realization from the pass count -- rl_prev is then not carried through the loop)
+            if constexpr (kAhead) rl_prev = blockIdx.x + (uint64_t)(it - 1) * step;
             wg_account(totals, ts, tb, s_rec[buf * (kRec + 1) + 2 * NT * NR].x != 0.0, rl_prev, sym_out, bit_out);
         }
         wg_flush(totals, counters, (unsigned long long)per_sym * pp.n_ofdm_sym, (unsigned long long)per_sym * pp.n_ofdm_sym * mp.bits);
