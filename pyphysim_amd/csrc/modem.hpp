@@ -110,18 +110,32 @@ template <typename T> struct ModemParams {
     unsigned quad_lut;   // cert == 2: label of quadrant (re < 0) | (im < 0) << 1, a byte each
     T quad_lo, quad_hi;  // cert == 2: the certificate holds for lo <= |re|, |im| <= hi
 };
+// The literal metric |c - r|^2 of every search below and of walk_sweep (walk_f64.hpp) as ONE expression.  Written dx * dx + dy * dy at
+// each site, -ffp-contract=fast lets the compiler fuse either product into the sum, and it chose differently for the first
+// candidate and for the rest of one and the same search (walk_sweep<float>; demod_grid_multi_search on double2 with K >= 2): two
+// entries that are mirror images in an axis the point lies on, or duplicates -- the same numbers -- then compared unequal by one
+// rounding and the LATER index won an exact tie (tests/test_gpu_decide_forms.py: 64-QAM complex128 at (-0, -1.4186162239480016),
+// label 47 for 42).  An explicit fused multiply-add leaves the compiler nothing to choose: same instructions, one result.
+__device__ __forceinline__ float dist2(float2 r, float2 c) {
+    const float dx = r.x - c.x, dy = r.y - c.y;
+    return __builtin_fmaf(dx, dx, dy * dy);
+}
+__device__ __forceinline__ double dist2(double2 r, double2 c) {
+    const double dx = r.x - c.x, dy = r.y - c.y;
+    return __builtin_fma(dx, dx, dy * dy);
+}
+
 // exhaustive minimum distance over a table held in LDS; strict '<' keeps the FIRST minimum,
 // which is numpy.argmin's tie rule (fundamental.py:245).  The reference compares |c - r|; we
 // compare |c - r|^2 (same ordering away from rounding-level ties).
 template <typename T>
 __device__ __forceinline__ int demod_mindist(const cx<T>* __restrict__ s_table, int M, cx<T> r) {
-    T best = (r.x - s_table[0].x) * (r.x - s_table[0].x) + (r.y - s_table[0].y) * (r.y - s_table[0].y);
+    T best = dist2(r, s_table[0]);
     int idx = 0;
 #pragma unroll 8
     for (int m = 1; m < M; ++m) {
         const cx<T> c = s_table[m];
-        const T dx = r.x - c.x, dy = r.y - c.y;
-        const T d = dx * dx + dy * dy;
+        const T d = dist2(r, c);
         if (d < best) {
             best = d;
             idx = m;
@@ -185,8 +199,8 @@ __device__ __forceinline__ int demod_grid_search(const float2* __restrict__ s_ta
     int idx = idx0;
     const int m1 = n > 1 ? (int)((lo >> 16) & 0xFFu) : idx0;
     const float2 c0 = s_table[idx0], c1 = s_table[m1];
-    float best = (r.x - c0.x) * (r.x - c0.x) + (r.y - c0.y) * (r.y - c0.y);
-    const float d1 = (r.x - c1.x) * (r.x - c1.x) + (r.y - c1.y) * (r.y - c1.y);
+    float best = dist2(r, c0);
+    const float d1 = dist2(r, c1);
     if (d1 < best) {
         best = d1;
         idx = m1;
@@ -194,8 +208,7 @@ __device__ __forceinline__ int demod_grid_search(const float2* __restrict__ s_ta
     if (n > 2) {
         const int m2 = (int)(lo >> 24), m3 = n > 3 ? (int)(hi & 0xFFu) : idx0;
         const float2 c2 = s_table[m2], c3 = s_table[m3];
-        const float d2 = (r.x - c2.x) * (r.x - c2.x) + (r.y - c2.y) * (r.y - c2.y);
-        const float d3 = (r.x - c3.x) * (r.x - c3.x) + (r.y - c3.y) * (r.y - c3.y);
+        const float d2 = dist2(r, c2), d3 = dist2(r, c3);
         if (d2 < best) {
             best = d2;
             idx = m2;
@@ -209,9 +222,7 @@ __device__ __forceinline__ int demod_grid_search(const float2* __restrict__ s_ta
     for (int j = 4; j < n; ++j) {
         w >>= 8;
         const int m = (int)(w & 0xFFull);
-        const float2 c = s_table[m];
-        const float dx = r.x - c.x, dy = r.y - c.y;
-        const float d = dx * dx + dy * dy;
+        const float d = dist2(r, s_table[m]);
         if (d < best) {
             best = d;
             idx = m;
@@ -235,8 +246,8 @@ __device__ __forceinline__ int demod_grid_search(const double2* __restrict__ s_t
     int idx = idx0;
     const int m1 = n > 1 ? (int)((lo >> 16) & 0xFFu) : idx0;
     const double2 c0 = s_table[idx0], c1 = s_table[m1];
-    double best = (r.x - c0.x) * (r.x - c0.x) + (r.y - c0.y) * (r.y - c0.y);
-    const double d1 = (r.x - c1.x) * (r.x - c1.x) + (r.y - c1.y) * (r.y - c1.y);
+    double best = dist2(r, c0);
+    const double d1 = dist2(r, c1);
     if (d1 < best) {
         best = d1;
         idx = m1;
@@ -244,8 +255,7 @@ __device__ __forceinline__ int demod_grid_search(const double2* __restrict__ s_t
     if (n > 2) {                           // small constellations rarely get here
         const int m2 = (int)(lo >> 24), m3 = n > 3 ? (int)(hi & 0xFFu) : idx0;
         const double2 c2 = s_table[m2], c3 = s_table[m3];
-        const double d2 = (r.x - c2.x) * (r.x - c2.x) + (r.y - c2.y) * (r.y - c2.y);
-        const double d3 = (r.x - c3.x) * (r.x - c3.x) + (r.y - c3.y) * (r.y - c3.y);
+        const double d2 = dist2(r, c2), d3 = dist2(r, c3);
         if (d2 < best) {
             best = d2;
             idx = m2;
@@ -259,9 +269,7 @@ __device__ __forceinline__ int demod_grid_search(const double2* __restrict__ s_t
     for (int j = 4; j < n; ++j) {          // lists of five to seven: rare (cells at a corner of four regions of a dense set)
         w >>= 8;
         const int m = (int)(w & 0xFFull);
-        const double2 c = s_table[m];
-        const double dx = r.x - c.x, dy = r.y - c.y;
-        const double d = dx * dx + dy * dy;
+        const double d = dist2(r, s_table[m]);
         if (d < best) {
             best = d;
             idx = m;
@@ -303,6 +311,9 @@ __device__ __forceinline__ int demod_grid4_search(const float4* __restrict__ s_t
 // per symbol are evaluated as K independent LDS round trips per step (a symbol with fewer candidates re-evaluates its
 // current best, which the strict '<' ignores).  Cells with more than four candidates, or the 0xFF "sweep
 // everything" marker, take demod_grid4's loop.  Same decisions as demod_grid4 / demod_mindist_multi.
+// (The candidate bytes of a cell word index s_tab4 BEFORE the count is looked at: a marker word must be the BARE 0xFF that
+// build_demod_grid writes -- every candidate byte 0, a valid index -- and tests/test_decide_forms_cpu.py holds the builder to that;
+// the double2 form below guards the marker explicitly.)
 template <int K>
 __device__ __forceinline__ void demod_grid4_multi_search(const float4* __restrict__ s_tab4,
                                                   const unsigned long long* __restrict__ s_grid, const DemodGrid& g, int M,
@@ -364,9 +375,7 @@ __device__ __forceinline__ void demod_grid_multi_search(const double2* __restric
         n[k] = (int)(w[k] & 0xFFull);
         slow = slow || n[k] > 4;
         idx[k] = n[k] == 0xFF ? 0 : (int)((w[k] >> 8) & 0xFFull);
-        const double2 c = s_table[idx[k]];
-        const double dx = r[k].x - c.x, dy = r[k].y - c.y;
-        best[k] = dx * dx + dy * dy;
+        best[k] = dist2(r[k], s_table[idx[k]]);
     }
 #pragma unroll
     for (int j = 1; j < 4; ++j) {
@@ -379,8 +388,7 @@ __device__ __forceinline__ void demod_grid_multi_search(const double2* __restric
         }
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-            const double dx = r[k].x - c[k].x, dy = r[k].y - c[k].y;
-            const double d = dx * dx + dy * dy;
+            const double d = dist2(r[k], c[k]);
             if (d < best[k]) {
                 best[k] = d;
                 idx[k] = m[k];

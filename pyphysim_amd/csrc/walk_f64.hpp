@@ -78,13 +78,11 @@ __device__ __forceinline__ uint32_t walk_wave_total(uint32_t v) {
 
 // the literal sweep (strict '<': numpy.argmin's first minimum, fundamental.py:241-246), rolled: it runs once in ~1e8 symbols
 template <typename T> __device__ __forceinline__ int walk_sweep(const cx<T>* __restrict__ s_table, int M, cx<T> r) {
-    T best = (r.x - s_table[0].x) * (r.x - s_table[0].x) + (r.y - s_table[0].y) * (r.y - s_table[0].y);
+    T best = dist2(r, s_table[0]);        // (one expression for every candidate: modem.hpp dist2)
     int idx = 0;
 #pragma unroll 1
     for (int m = 1; m < M; ++m) {
-        const cx<T> c = s_table[m];
-        const T dx = r.x - c.x, dy = r.y - c.y;
-        const T d = dx * dx + dy * dy;
+        const T d = dist2(r, s_table[m]);
         if (d < best) {
             best = d;
             idx = m;
