@@ -1100,6 +1100,72 @@ int mcle_run_ia_quantized(mcle_ctx* ctx, int dtype, const mcle_ia_cfg* cfg, cons
                           uint32_t* d_bit_err, double* d_sum_capacity, uint32_t* d_iterations, int32_t* d_index,
                           double* d_dist_sum);
 
+/* ---- indoor system level: METIS test case 2, one floor (apps/metis_scenarios/simulate_metis_scenario.py, ..._scenario2.py) ---
+ * The floor is rooms_per_side x rooms_per_side square rooms of side_length metres, centres as calc_room_positions_square gives
+ * them (row 0 on top; the shift keeps the reference's floor division, so side_length 7.5 with 4 rooms per side has centres -11,
+ * -3.5, 4, 11.5).  Access points (APs) stand in the room centres chosen by ap_decimation (get_ap_positions: 1 every room, 2 a
+ * checkerboard, 4 odd rows and columns, 9 every third from 1), numbered in row-major order of their rooms.
+ * A point's room is the room with the nearest centre (per axis, the lowest index on a tie).  walls(room, AP) is the Manhattan
+ * distance of the room indices; the host shows per configuration that this is the reference's round(|Re| + |Im|) of
+ * (room - 1.0001 AP) / side_length and refuses a configuration where it is not.  Positions, rooms and walls are f64 / integer
+ * in either arithmetic; from the squared distance on everything is `dtype`.
+ *     gain g[u][a] = pl(d, walls) 10^(-walls wall_loss_dB / 10),  pl the model's linear path gain with the small-distance
+ *     clamp (a negative loss in dB is 0 dB, d = 0 included):
+ *       MCLE_INDOOR_PL_NONE       pl = 1
+ *       MCLE_INDOOR_PL_GENERAL    10 n log10(d dist_scale) + C dB   (PathLoss3GPP1 on metres: 3.76, 128.1, 1e-3; PathLossFreeSpace)
+ *       MCLE_INDOOR_PL_METIS_PS7  walls = 0: 18.7 log10 d + 46.8 + 20 log10(fc_GHz / 5);
+ *                                 walls > 0: 36.8 log10 d + 43.8 + 20 log10(fc_GHz / 5) + 5 (walls - 1)       (d in metres)
+ *     association a*: assoc 0 the closest AP (argmin of the distance), 1 the best channel (argmax of g); the lowest index on an
+ *     exact tie.
+ *     SINR = tx g[u][a*] / (sum over transmitting a != a* of tx g[u][a] + noise), reported as 10 log10.
+ * The interference is summed over a != a* directly, never as total minus desired.
+ *
+ * mcle_indoor_sinr: the heat-map operator.  d_points [n][2] (x, y in metres) -> d_sinr_dB [n] and d_assoc [n] (either may be
+ * NULL).  Every AP transmits: active must be 0; n_users and the histogram fields are ignored.
+ *
+ * mcle_run_indoor_drops: Monte Carlo over user drops, one drop per wavefront.  Drop r (realization first + r of mcle-philox-v1)
+ * places n_users users: user u at n L (u_x - 0.5) + j n L (u_y - 0.5) with u_x, u_y the uniforms 2 u and 2 u + 1 of STREAM_CHAN
+ * (n = rooms_per_side, L = side_length), or at d_positions [count][U][2] when that is not NULL.  active 1 switches off every AP
+ * that no user of the drop chose (simulate_metis_scenario2.py); active 0 leaves all on.
+ *     capacity[u] = log2(1 + SINR) / (users of this drop on a*)                         (f64 from the dtype SINR)
+ *     d_sinr_dB, d_capacity, d_assoc [count][U];  d_sum_capacity, d_sum_sinr_dB, d_min_sinr_dB [count]: over the drop's users;
+ *     d_active_aps [count]: the drop's transmitting APs (all of them with active 0);
+ *     d_hist [hist_bins + 2]: users by SINR in dB -- slot 0 below hist_lo_dB, slot 1 + floor((s - lo) / step) up to hist_bins,
+ *     slot hist_bins + 1 at or above the top;  d_load_hist [U + 1]: slot k counts the (drop, AP) pairs with k users.
+ * Both histograms ACCUMULATE into the caller's zeroed uint64 counters (exact integers).  Every output pointer may be NULL;
+ * outputs are double in either arithmetic.
+ * Every output of a drop is a function of (seed, drop, cfg, dtype) alone: bit for bit independent of the grid, of
+ * MCLE_OPT_GRID_OVERSUB and of how [first, first + count) is split (per-drop sums are taken in a fixed lane order).
+ * Envelope: rooms_per_side 1 .. 16, ap_decimation 1 / 2 / 4 / 9 with at least one AP, n_users 1 .. 256, hist_bins 0 .. 256
+ * (hist_step_dB > 0 with bins), side_length > 0, wall_loss_dB >= 0, tx_power > 0, noise_power > 0 (in f32 both must be normal
+ * f32 numbers, 1.18e-38 .. 3.4e38: they are rounded to f32, and a zero noise power would make a lone AP's SINR infinite), GENERAL: pl_n > 0 and
+ * dist_scale > 0, PS7: fc_MHz > 0, n and count <= 2^31-1; anything else is MCLE_E_INVAL with a message that names the argument
+ * (the shape rules are checked before the context and the pointers).  n = 0 / count = 0 returns MCLE_OK and launches nothing.
+ * mcle_ctx_last_kernel: "indoor_sinr f64|f32 m<model> a<assoc>", "indoor_drops f64|f32 m<model> a<assoc> t<active> u<users per
+ * lane: 1, 2 or 4>". */
+enum { MCLE_INDOOR_PL_NONE = 0, MCLE_INDOOR_PL_GENERAL = 1, MCLE_INDOOR_PL_METIS_PS7 = 2 };
+typedef struct mcle_indoor_cfg {
+    int32_t rooms_per_side;   /* 1..16 */
+    int32_t ap_decimation;    /* 1, 2, 4, 9; a layout with no AP is MCLE_E_INVAL */
+    int32_t model;            /* MCLE_INDOOR_PL_* */
+    int32_t assoc;            /* 0 closest AP (argmin distance), 1 best channel (argmax gain) */
+    int32_t active;           /* 0 every AP transmits, 1 only APs some user chose (drops only) */
+    int32_t n_users;          /* drops only: 1..256 */
+    int32_t hist_bins;        /* 0..256 */
+    int32_t reserved;
+    double side_length, wall_loss_dB;
+    double pl_n, pl_C, dist_scale;  /* GENERAL: 10 n log10(d * dist_scale) + C (3GPP: 3.76, 128.1, 1e-3) */
+    double fc_MHz;                  /* METIS PS7 */
+    double tx_power, noise_power;   /* linear */
+    double hist_lo_dB, hist_step_dB;
+} mcle_indoor_cfg;
+int mcle_indoor_sinr(mcle_ctx* ctx, int dtype, const mcle_indoor_cfg* cfg, const double* d_points, size_t n, double* d_sinr_dB,
+                     int32_t* d_assoc);
+int mcle_run_indoor_drops(mcle_ctx* ctx, int dtype, const mcle_indoor_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
+                          const double* d_positions, uint64_t* d_hist, uint64_t* d_load_hist, double* d_sum_capacity,
+                          double* d_sum_sinr_dB, double* d_min_sinr_dB, int32_t* d_active_aps, double* d_sinr_dB,
+                          double* d_capacity, int32_t* d_assoc);
+
 /* ---- same-seed parity mode: NumPy's legacy global RandomState replayed on the device -------
  * Realization r receives exactly what the reference draws after np.random.seed(seed_base + r)
  * (legacy MT19937; util/misc.py:327-355 randn_c = randn real block then imag block, and

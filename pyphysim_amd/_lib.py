@@ -187,6 +187,18 @@ class QuantCfg(Structure):
 QUANT_METRICS = {"euclidean": 0, "chordal": 1}
 
 
+class IndoorCfg(Structure):
+    _fields_ = [("rooms_per_side", c_int32), ("ap_decimation", c_int32), ("model", c_int32), ("assoc", c_int32),
+                ("active", c_int32), ("n_users", c_int32), ("hist_bins", c_int32), ("reserved", c_int32),
+                ("side_length", c_double), ("wall_loss_dB", c_double), ("pl_n", c_double), ("pl_C", c_double),
+                ("dist_scale", c_double), ("fc_MHz", c_double), ("tx_power", c_double), ("noise_power", c_double),
+                ("hist_lo_dB", c_double), ("hist_step_dB", c_double)]
+
+
+INDOOR_MODELS = {"none": 0, "general": 1, "metis_ps7": 2}
+INDOOR_ASSOC = {"closest": 0, "best_channel": 1}
+
+
 class LegacySeg(Structure):
     _fields_ = [("kind", c_int32), ("n", c_int32), ("range", c_uint32), ("reserved", c_uint32)]
 
@@ -307,6 +319,9 @@ _PROTOS = {
     "mcle_quantize_links": (c_int, [_P, c_int, POINTER(QuantCfg), _P, _P, _P, _P, _P, c_size_t]),
     "mcle_run_ia_quantized": (c_int, [_P, c_int, POINTER(IaCfg), POINTER(QuantCfg), _P, c_uint64, c_uint64, c_uint64, _P, _P, _P,
                                       _P, _P, _P, _P]),
+    "mcle_indoor_sinr": (c_int, [_P, c_int, POINTER(IndoorCfg), _P, c_size_t, _P, _P]),
+    "mcle_run_indoor_drops": (c_int, [_P, c_int, POINTER(IndoorCfg), c_uint64, c_uint64, c_uint64, _P, _P, _P, _P, _P, _P, _P, _P,
+                                      _P, _P]),
     "mcle_legacy_draws": (c_int, [_P, POINTER(LegacySeg), c_int, c_uint32, c_uint64, c_uint64, _P, c_size_t, _P,
                                   c_size_t, _P]),
     "mcle_complex_from_parts": (c_int, [_P, c_int, _P, _P, c_double, _P, c_size_t]),

@@ -997,6 +997,84 @@ class Engine:
                 out[2] = out[2][0]
         return tuple(out)
 
+    # ---- indoor system level (mcle_indoor_sinr / mcle_run_indoor_drops; csrc/pipeline_indoor.hip) ----
+    @staticmethod
+    def _indoor_cfg(rooms_per_side, side_length, ap_decimation, model, assoc, active, n_users, wall_loss_dB, tx_power,
+                    noise_power, pl_n, pl_C, dist_scale, fc_MHz, hist_bins=0, hist_lo_dB=0.0, hist_step_dB=1.0):
+        return _lib.IndoorCfg(int(rooms_per_side), int(ap_decimation), int(_lib.INDOOR_MODELS.get(model, model)),
+                              int(_lib.INDOOR_ASSOC.get(assoc, assoc)), int(active), int(n_users), int(hist_bins), 0,
+                              float(side_length), float(wall_loss_dB), float(pl_n), float(pl_C), float(dist_scale),
+                              float(fc_MHz), float(tx_power), float(noise_power), float(hist_lo_dB), float(hist_step_dB))
+
+    def indoor_sinr(self, points, rooms_per_side, side_length, ap_decimation=1, model="metis_ps7", assoc="closest",
+                    wall_loss_dB=5.0, tx_power=0.1, noise_power=1e-13, pl_n=3.76, pl_C=128.1, dist_scale=1e-3, fc_MHz=900.0,
+                    dtype=None, with_assoc=False):
+        """SINR in dB of every point of one floor of the METIS indoor scenario with every access point transmitting
+        (mcle_indoor_sinr; apps/metis_scenarios/simulate_metis_scenario.py).  points: complex (x + 1j y, metres) of any shape, or
+        real [..., 2].  model 'none' / 'general' (10 pl_n log10(d dist_scale) + pl_C dB) / 'metis_ps7'; assoc 'closest' /
+        'best_channel'; powers linear.  Returns float64 of the points' shape (and the chosen AP indices with with_assoc)."""
+        dt = self._dt(dtype)
+        pts = np.asarray(points)
+        if np.iscomplexobj(pts):
+            shape = pts.shape
+            xy = np.ascontiguousarray(pts, dtype=np.complex128).reshape(-1).view(np.float64)
+        else:
+            if pts.ndim < 1 or pts.shape[-1] != 2:
+                raise ValueError("points must be complex or real [..., 2] (got %s)" % (pts.shape,))
+            shape = pts.shape[:-1]
+            xy = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1)
+        n = xy.size // 2
+        cfg = self._indoor_cfg(rooms_per_side, side_length, ap_decimation, model, assoc, 0, 0, wall_loss_dB, tx_power,
+                               noise_power, pl_n, pl_C, dist_scale, fc_MHz)
+        d_xy = self.to_device(xy)
+        sinr = self.empty(n, np.float64)
+        idx = self.empty(n, np.int32) if with_assoc else None
+        self._raise_value(self.lib.mcle_indoor_sinr(self.ctx, dt, byref(cfg), d_xy.ptr, n, sinr.ptr,
+                                                    idx.ptr if with_assoc else None))
+        out = sinr.get().reshape(shape)
+        return (out, idx.get().reshape(shape)) if with_assoc else out
+
+    def run_indoor_drops(self, rooms_per_side, side_length, ap_decimation, n_users, seed, first, count, model="metis_ps7",
+                         assoc="best_channel", active=True, wall_loss_dB=5.0, tx_power=0.1, noise_power=1e-13, pl_n=3.76,
+                         pl_C=128.1, dist_scale=1e-3, fc_MHz=900.0, hist_bins=0, hist_lo_dB=0.0, hist_step_dB=1.0,
+                         positions=None, dtype=None, per_user=False):
+        """`count` user drops on one floor of the METIS indoor scenario (mcle_run_indoor_drops;
+        apps/metis_scenarios/simulate_metis_scenario2.py, one drop per call there): drop r places n_users users from the Philox
+        draws of realization first + r (or at positions [count, n_users], complex or real [..., 2]), each user takes its AP,
+        with `active` the APs nobody chose are switched off.  Returns a dict: 'hist' [hist_bins + 2] and 'load_hist'
+        [n_users + 1] (exact integer counts), 'sum_capacity', 'sum_sinr_dB', 'min_sinr_dB', 'active_aps' [count]; with
+        per_user also 'sinr_dB', 'capacity', 'assoc' [count, n_users]."""
+        dt = self._dt(dtype)
+        count, U = int(count), int(n_users)
+        cfg = self._indoor_cfg(rooms_per_side, side_length, ap_decimation, model, assoc, bool(active), U, wall_loss_dB,
+                               tx_power, noise_power, pl_n, pl_C, dist_scale, fc_MHz, hist_bins, hist_lo_dB, hist_step_dB)
+        d_pos = None
+        if isinstance(positions, DeviceArray):           # resident float64 [count, n_users, 2]
+            if positions.dtype != np.dtype(np.float64) or positions.size != count * U * 2:
+                raise ValueError("device positions must be float64 [count, n_users, 2]")
+            d_pos = positions
+        elif positions is not None:
+            pos = np.asarray(positions)
+            pos = (np.ascontiguousarray(pos, dtype=np.complex128).reshape(-1).view(np.float64) if np.iscomplexobj(pos)
+                   else np.ascontiguousarray(pos, dtype=np.float64).reshape(-1))
+            if pos.size != count * U * 2:
+                raise ValueError("positions must hold count x n_users points (got %d values)" % pos.size)
+            d_pos = self.to_device(pos)
+        bins = max(int(hist_bins), 0)
+        hist, load = self.zeros(bins + 2, np.uint64), self.zeros(max(U, 0) + 1, np.uint64)
+        per_drop = [self.empty(count, np.float64) for _ in range(3)]
+        act = self.empty(count, np.int32)
+        per = [self.empty((count, max(U, 0)), t) for t in (np.float64, np.float64, np.int32)] if per_user else [None] * 3
+        ptr = lambda a: a.ptr if a is not None else None
+        self._raise_value(self.lib.mcle_run_indoor_drops(self.ctx, dt, byref(cfg), int(seed), int(first), count, ptr(d_pos),
+                                                         hist.ptr, load.ptr, per_drop[0].ptr, per_drop[1].ptr, per_drop[2].ptr,
+                                                         act.ptr, ptr(per[0]), ptr(per[1]), ptr(per[2])))
+        res = dict(hist=hist.get(), load_hist=load.get(), sum_capacity=per_drop[0].get(), sum_sinr_dB=per_drop[1].get(),
+                   min_sinr_dB=per_drop[2].get(), active_aps=act.get())
+        if per_user:
+            res.update(sinr_dB=per[0].get(), capacity=per[1].get(), assoc=per[2].get())
+        return res
+
     def ia_iterative(self, solver, big_H, F_init, noise_var, max_iterations=50, relative_factor=1e-6,
                      initialize_with="fix"):
         """IterativeIASolverBaseClass.solve (algorithms.py:802-883) with initialize_with='fix': big_H

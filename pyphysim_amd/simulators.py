@@ -795,6 +795,95 @@ class CompSimulator(BatchedSimulationRunner):
         return res
 
 
+class MetisDropSimulator(BatchedSimulationRunner):
+    """Monte Carlo over user drops on one floor of the METIS indoor scenario (the reference's
+    apps/metis_scenarios/simulate_metis_scenario2.py runs ONE drop per call): `num_rooms_per_side`^2 square rooms of
+    `side_length` metres, APs by `ap_decimation` (1, 2, 4, 9), `num_users` users dropped uniformly, best-channel association on
+    METIS PS7 plus `single_wall_loss_dB` per wall, the APs nobody chose switched off (`active_only=False` leaves all on).  A
+    repetition is a drop; one Engine.run_indoor_drops per batch.  Any of the scalars may be a list: every combination is one
+    parameter variation.
+
+    Results: 'sinr_dB' and 'capacity' (RATIO against users: the mean per user), 'sum_capacity' and 'active_aps' (RATIO against
+    drops), 'sinr_histogram' (CHOICE over hist_bins + 2 slots of width hist_step_dB from hist_lo_dB: below, the bins, at or
+    above the top).  Sums and the histogram travel through EXTRA_KEYS, so sharding and partial-result resume keep them."""
+
+    _SUMS = ("users", "sinr_dB_sum", "sinr_dB_sq", "capacity_sum", "capacity_sq", "active_aps_sum", "active_aps_sq")
+    _SCALARS = ("num_rooms_per_side", "side_length", "single_wall_loss_dB", "ap_decimation", "Pt_dBm", "noise_power_dBm",
+                "num_users")
+
+    def __init__(self, num_rooms_per_side=12, side_length=10.0, single_wall_loss_dB=5.0, ap_decimation=1, Pt_dBm=20.0,
+                 noise_power_dBm=None, num_users=100, rep_max=1000, fc_MHz=900.0, active_only=True, hist_bins=60,
+                 hist_lo_dB=-10.0, hist_step_dB=1.0, seed=0, batch_size=4096, dtype="f32", engine=None,
+                 common_random_numbers=False, process_group=None):
+        super().__init__(batch_size=batch_size, process_group=process_group)
+        if noise_power_dBm is None:
+            from .noise import calc_thermal_noise_power_dBm
+            noise_power_dBm = calc_thermal_noise_power_dBm(25, 5e6)
+        self.rep_max = rep_max
+        self.seed = int(seed)
+        self.dtype = dtype
+        self.common_random_numbers = common_random_numbers
+        self._engine = engine
+        self.fc_MHz, self.active_only = float(fc_MHz), bool(active_only)
+        self.hist_bins, self.hist_lo_dB, self.hist_step_dB = int(hist_bins), float(hist_lo_dB), float(hist_step_dB)
+        self.EXTRA_KEYS = self._SUMS + tuple("sinr_h%d" % i for i in range(self.hist_bins + 2))
+        self.EXTRA_INT_KEYS = ("users", "active_aps_sum", "active_aps_sq") + self.EXTRA_KEYS[len(self._SUMS):]
+        values = dict(zip(self._SCALARS, (num_rooms_per_side, side_length, single_wall_loss_dB, ap_decimation, Pt_dBm,
+                                          noise_power_dBm, num_users)))
+        for k, v in values.items():
+            if np.ndim(v) > 0:
+                self.params.add(k, np.asarray(v))
+                self.params.set_unpack_parameter(k)
+            else:
+                self.params.add(k, v)
+
+    engine = _LinkSimulator.engine
+    _seed_for = _LinkSimulator._seed_for
+
+    def drop_args(self, current_parameters):
+        """The variation as keyword arguments of Engine.run_indoor_drops."""
+        from .util import dBm2Linear
+        p = current_parameters
+        return dict(rooms_per_side=int(p["num_rooms_per_side"]), side_length=float(p["side_length"]),
+                    ap_decimation=int(p["ap_decimation"]), n_users=int(p["num_users"]), model="metis_ps7",
+                    assoc="best_channel", active=self.active_only, wall_loss_dB=float(p["single_wall_loss_dB"]),
+                    tx_power=float(dBm2Linear(p["Pt_dBm"])), noise_power=float(dBm2Linear(p["noise_power_dBm"])),
+                    fc_MHz=self.fc_MHz, hist_bins=self.hist_bins, hist_lo_dB=self.hist_lo_dB, hist_step_dB=self.hist_step_dB,
+                    dtype=self.dtype)
+
+    def _run_batch(self, current_parameters, first_rep, count):
+        out = self.engine.run_indoor_drops(seed=self._seed_for(current_parameters), first=first_rep, count=count,
+                                           **self.drop_args(current_parameters))
+        c = {k: 0 for k in self.COUNTER_KEYS + ("n_symbols", "n_bits")}
+        c["n_realizations"] = int(count)
+        U = int(current_parameters["num_users"])
+        mean_db, mean_cap = out["sum_sinr_dB"] / U, out["sum_capacity"] / U        # one RATIO update per drop
+        act = out["active_aps"].astype(np.int64)
+        c.update(users=int(count) * U, sinr_dB_sum=float(mean_db.sum()), sinr_dB_sq=float(np.square(mean_db).sum()),
+                 capacity_sum=float(out["sum_capacity"].sum()), capacity_sq=float(np.square(out["sum_capacity"]).sum()),
+                 active_aps_sum=int(act.sum()), active_aps_sq=int(np.square(act).sum()))
+        for i, h in enumerate(out["hist"].tolist()):
+            c["sinr_h%d" % i] = int(h)
+        return c
+
+    def _results_from_counters(self, current_parameters, c):
+        from .simulations import Result, SimulationResults
+        res = SimulationResults()
+        n = int(c["n_realizations"])
+        gf = lambda k: float(c.get(k, 0.0))
+        users, U = int(round(gf("users"))), int(current_parameters["num_users"])
+        cap, cap_sq = gf("capacity_sum"), gf("capacity_sq")
+        res.add_result(Result.from_batch("sinr_dB", Result.RATIOTYPE, gf("sinr_dB_sum") * U, users, gf("sinr_dB_sum"),
+                                         gf("sinr_dB_sq"), n))
+        res.add_result(Result.from_batch("capacity", Result.RATIOTYPE, cap, users, cap / U, cap_sq / (U * U), n))
+        res.add_result(Result.from_batch("sum_capacity", Result.RATIOTYPE, cap, n, cap, cap_sq, n))
+        act, act_sq = int(round(gf("active_aps_sum"))), int(round(gf("active_aps_sq")))
+        res.add_result(Result.from_batch("active_aps", Result.RATIOTYPE, act, n, float(act), float(act_sq), n))
+        hist = [int(round(gf("sinr_h%d" % i))) for i in range(self.hist_bins + 2)]
+        res.add_result(Result.from_histogram("sinr_histogram", hist))
+        return res
+
+
 class GeneralIaSimulator(BatchedSimulationRunner):
     """The IA link on any geometry the general solver covers (the reference's apps/ia/simulate_ia.py with Nr, Nt, Ns as
     parameters -- apps/ia/IA_Results_NrxNt(Ns).py runs K = 3, Nr = 5, Nt = 3, Ns = 2 -- and apps/ia/simulate_greedy_ia.py,
