@@ -597,7 +597,8 @@ int mcle_run_mimo_ofdm(mcle_ctx* ctx, int dtype, const mcle_mimo_ofdm_cfg* cfg, 
                        uint64_t first, uint64_t count, mcle_counters* d_counters,
                        uint32_t* d_sym_err, uint32_t* d_bit_err);
 
-/* The reference's MIMO application, any of its six schemes, fused. */
+/* The reference's MIMO application, any of its six schemes, fused.  max(nt, nr) * n_symbols <= 2^31 - 1 (draw positions are
+ * 32-bit) and count <= 2^31 - 1 per call; anything else: MCLE_E_INVAL. */
 int mcle_run_mimo_flat(mcle_ctx* ctx, int dtype, const mcle_mimo_flat_cfg* cfg, uint64_t seed,
                        uint64_t first, uint64_t count, mcle_counters* d_counters,
                        uint32_t* d_sym_err, uint32_t* d_bit_err);
@@ -643,7 +644,8 @@ int mcle_run_mimo_ofdm_tdl(mcle_ctx* ctx, int dtype, const mcle_mimo_ofdm_tdl_cf
 
 /* d_sum_capacity (may be NULL): per-realization sum_k log2(1 + SINR_k) of the chosen solution */
 /* d_iterations (may be NULL): per-realization runned_iterations of an iterative solver.  Iterative solvers
- * draw their random initial precoders (randomizeF, iabase.py:538-540) from stream 3 of the realization. */
+ * draw their random initial precoders (randomizeF, iabase.py:538-540) from stream 3 of the realization.
+ * 6 * n_symbols <= 2^31 - 1 (six receive antennas' noise rows; draw positions are 32-bit) and count <= 2^31 - 1 per call. */
 int mcle_run_ia(mcle_ctx* ctx, int dtype, const mcle_ia_cfg* cfg, uint64_t seed, uint64_t first,
                 uint64_t count, mcle_counters* d_counters, uint32_t* d_sym_err, uint32_t* d_bit_err,
                 double* d_sum_capacity, uint32_t* d_iterations);
@@ -801,7 +803,8 @@ typedef struct mcle_bd_cfg {            /* apps/comp_BD/simulate_comp_simple.py:
     double bd_noise_var;                /* noise variance handed to the water-filling (the app passes 1e-50) */
     double pathloss[16];
 } mcle_bd_cfg;
-/* Fused: channel draw, block diagonalisation, precoding, channel + noise, zero forcing, demodulation, counts. */
+/* Fused: channel draw, block diagonalisation, precoding, channel + noise, zero forcing, demodulation, counts.
+ * K * nr * n_symbols <= 2^31 - 1 (draw positions are 32-bit) and count <= 2^31 - 1 per call. */
 int mcle_run_bd(mcle_ctx* ctx, int dtype, const mcle_bd_cfg* cfg, uint64_t seed, uint64_t first,
                 uint64_t count, mcle_counters* d_counters, uint32_t* d_sym_err, uint32_t* d_bit_err);
 
@@ -1085,7 +1088,8 @@ int mcle_run_codebook_search(mcle_ctx* ctx, int dtype, const mcle_codebook_cfg* 
  * run and a quantized run of one seed are on common random numbers.  A singular quantized system is flagged skipped as today.
  * d_sum_capacity: sum_k log2(1 + SINR_k), SINR_k = |G_kk|^2 / (sum_{l != k} |G_kl|^2 + noise_var ||U_k||^2) -- MultiUserChannelMatrix.
  * calc_SINR on the true channel (app :272-273), not the solver's own figure.  d_index (may be NULL) [count][3][3]; d_dist_sum (may
- * be NULL) [count]: the sum of the realization's nine chosen distances in link order.  qcfg: K = 3, nr = nt = 2. */
+ * be NULL) [count]: the sum of the realization's nine chosen distances in link order.  qcfg: K = 3, nr = nt = 2.  As for mcle_run_ia,
+ * 6 * n_symbols <= 2^31 - 1 (draw positions are 32-bit) and count <= 2^31 - 1 per call. */
 enum { MCLE_QUANT_EUCLIDEAN = 0, MCLE_QUANT_CHORDAL = 1 };
 typedef struct mcle_quant_cfg {
     int32_t K, nr, nt;                  /* 1 <= K <= 4, 1 <= nr, nt <= 6 : dim = nr*nt <= 36 */

@@ -26,6 +26,7 @@
 #include "totals.hpp"
 #include "wave_draws.hpp"
 #include "walk_f64.hpp"
+#include "link_walk.hpp"
 #include "bd_static.hpp"
 #include "bd_extint.hpp"
 
@@ -228,14 +229,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 4 || KC) ? 3 : 2) void k_bd_link
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     WgTotals& totals = totals_all[wv];
     __shared__ double s_bm[sizeof(T) == 8 ? kBmLdsDoubles : 1];   // complex128 Box-Muller tables (bm_f64.hpp)
-    if constexpr (sizeof(T) == 8) bm_tables_to_lds(s_bm, (int)threadIdx.x, (int)blockDim.x);
-    load_table(mp, s_table);
-    load_grid(mp, s_grid);
-    if constexpr (sizeof(T) == 4)
-        for (int m = threadIdx.x; m < mp.M; m += blockDim.x) {
-            const float2 c = mp.g_table[m];
-            s_tab4[m] = make_float4(c.x, c.y, 0.5f * (c.x * c.x + c.y * c.y), 0.f);
-        }
+    link_prologue(mp, s_table, s_tab4, s_grid, s_bm);
     const int lane = threadIdx.x & 63;
     const T sigma = (T)sqrt(pp.noise_var);
     const uint32_t mask = (uint32_t)(mp.M - 1);
@@ -349,9 +343,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 4 || KC) ? 3 : 2) void k_bd_link
                     column(tx, nz);
                 }
             }
-            se = wave_sum_u32(se);
-            be = wave_sum_u32(be);
-            if (lane == 0) wg_account(totals, se, be, !ok, rl, sym_out, bit_out);
+            link_account(totals, se, be, !ok, rl, lane, sym_out, bit_out);
         }
     }
     wg_flush_waves<4>(totals_all, counters, (unsigned long long)n * NS, (unsigned long long)n * NS * mp.bits);
@@ -362,90 +354,79 @@ static int launch_run_bd(mcle_ctx* ctx, const mcle_bd_cfg* cfg, const BdParams& 
                          uint64_t count, mcle_counters* d_counters, uint32_t* d_sym_err, uint32_t* d_bit_err) {
     const int n = cfg->K * R;
     const ModemParams<T> mp = pipe_modem<T>(ctx, cfg->demod_method);
-    int rc;
-    void* recs = nullptr;
     const uint64_t kSlice = 1ull << 20;          // realizations per solve + walk pair: bounds the record buffer
-    const uint64_t slice = count < kSlice ? count : kSlice;
     const size_t stride = (size_t)(n * (R + 1) + 1);
-    if ((rc = ctx->scratch((size_t)slice * stride * sizeof(cx<T>), &recs))) return rc;
     const size_t lds = (size_t)mp.grid.G * mp.grid.G * sizeof(unsigned long long);
     const int per_wave = 8;
-    for (uint64_t off = 0; off < count; off += slice) {
-        const uint64_t m = count - off < slice ? count - off : slice;
-        const dim3 sgrid((unsigned)((m + 63) / 64));
-        bool launched = false;
+    // (complex128: three wavefronts per SIMD where the user count is a compile-time constant -- 168 registers, nothing spilled --
+    //  two for the run-time-sized form, which spills 18 - 58 registers at that bound)
+    const bool kc = R <= 2 && (cfg->K == 2 || cfg->K == 3) && cfg->K * R <= kBdMaxN;
+    // demodulator path of the walk (compile-time in the kernel): complex64 min-distance in lockstep -- a sweep for M <= 8,
+    // certificate / candidate grid otherwise; everything else one demod_one per stream
+    // (round 5: a constellation WITH a certificate -- square QAM, QPSK -- goes through it whatever its size: the application's
+    //  own 4-PSK was swept point by point in lockstep, ~20 instructions per decision where the quadrant certificate takes 6)
+    const int mode = (sizeof(T) == 4 && mp.method == MCLE_DEMOD_MINDIST)
+                         ? ((mp.cert && mp.grid.G > 0) ? 2 : (mp.M <= 8 ? 1 : (mp.grid.G > 0 ? 2 : 0))) : 0;
+    return launch_sliced(
+        ctx, first, count, kSlice, stride * sizeof(cx<T>), d_sym_err, d_bit_err,
+        [&](void* recs, uint64_t at, uint64_t m) {
+            const dim3 sgrid((unsigned)((m + 63) / 64));
 #define MCLE_BD_STATIC(K_)                                                                                                \
-    if (!launched && cfg->K == K_ && K_ * R <= 6) {                                                                       \
+    if (cfg->K == K_ && K_ * R <= 6) {                                                                                    \
         hipLaunchKernelGGL((k_bd_solve_links_static<T, K_, (K_ * R <= 6 ? R : 1)>), sgrid, dim3(64), 0, ctx->stream, pp, seed,  \
-                           first + off, m, (cx<T>*)recs);                                                                \
-        launched = true;                                                                                                  \
+                           at, m, (cx<T>*)recs);                                                                          \
+        return;                                                                                                           \
     }
-        if (!ctx->opt[MCLE_OPT_BD_RUNTIME_SOLVE]) {       // compile-time-sized solve (registers) where n = K R <= 6
-            MCLE_BD_STATIC(2) MCLE_BD_STATIC(3) MCLE_BD_STATIC(4) MCLE_BD_STATIC(5) MCLE_BD_STATIC(6)
-        }
+            if (!ctx->opt[MCLE_OPT_BD_RUNTIME_SOLVE]) {       // compile-time-sized solve (registers) where n = K R <= 6
+                MCLE_BD_STATIC(2) MCLE_BD_STATIC(3) MCLE_BD_STATIC(4) MCLE_BD_STATIC(5) MCLE_BD_STATIC(6)
+            }
 #undef MCLE_BD_STATIC
-        if (!launched)
-            hipLaunchKernelGGL((k_bd_solve_links<T, R>), sgrid, dim3(64), 0, ctx->stream, pp, seed, first + off, m,
-                               (cx<T>*)recs);
-        MCLE_LAUNCH_CHECK();
-        // (complex128: three wavefronts per SIMD where the user count is a compile-time constant -- 168 registers, nothing spilled --
-        //  two for the run-time-sized form, which spills 18 - 58 registers at that bound)
-        const bool kc = R <= 2 && (cfg->K == 2 || cfg->K == 3) && cfg->K * R <= kBdMaxN;
-        // the resident set: the wavefronts per SIMD of k_bd_link's __launch_bounds__ (3 for complex64 and the compile-time user
-        // counts, 2 otherwise) -- rounds 4-5 sized the complex64 grid for four and ran a partial second wave of workgroups
-        const uint64_t cap = (uint64_t)ctx->n_cu * ((sizeof(T) == 4 || kc) ? 3 : 2);       // workgroups of four wavefronts
-        const uint64_t chunks = (m + per_wave - 1) / per_wave;
-        const unsigned grid = (unsigned)oversubscribed_grid(ctx, cap, (chunks + 3) / 4, 2);     // a chunk is 8-16 realizations; one chunk per workgroup measured 1.5 x slower
-        // demodulator path of the walk (compile-time in the kernel): complex64 min-distance in lockstep -- a sweep for M <= 8,
-        // certificate / candidate grid otherwise; everything else one demod_one per stream
-        // (round 5: a constellation WITH a certificate -- square QAM, QPSK -- goes through it whatever its size: the application's
-        //  own 4-PSK was swept point by point in lockstep, ~20 instructions per decision where the quadrant certificate takes 6)
-        const int mode = (sizeof(T) == 4 && mp.method == MCLE_DEMOD_MINDIST)
-                             ? ((mp.cert && mp.grid.G > 0) ? 2 : (mp.M <= 8 ? 1 : (mp.grid.G > 0 ? 2 : 0))) : 0;
-        bool walked = false;
-#define MCLE_BD_WALK(KC_, MODE_)                                                                                          \
-    if (!walked && (KC_ == 0 || (cfg->K == KC_ && KC_ * R <= kBdMaxN)) && mode == MODE_) {                                  \
-        hipLaunchKernelGGL((k_bd_link<T, R, (KC_ * R <= kBdMaxN ? KC_ : 0), (sizeof(T) == 4 ? MODE_ : 0)>), dim3(grid), dim3(256), lds, \
-                           ctx->stream, mp, pp, seed, first + off, m, per_wave, (const cx<T>*)recs, d_counters,           \
-                           d_sym_err ? d_sym_err + off : nullptr, d_bit_err ? d_bit_err + off : nullptr);                 \
-        walked = true;                                                                                                    \
-    }
-        if constexpr (R <= 2) {
-            // two or three users, an even number of columns >= 128: the packed walk of walk_f64.hpp (round 6; complex64 since its last day)
-            if (kc && link_walk_f64_fits(cfg->n_symbols) && !ctx->opt[MCLE_OPT_WALK_LEGACY]) {
+            hipLaunchKernelGGL((k_bd_solve_links<T, R>), sgrid, dim3(64), 0, ctx->stream, pp, seed, at, m, (cx<T>*)recs);
+        },
+        [&](void* recs, uint64_t at, uint64_t m, uint32_t* sym, uint32_t* bit) {
+            if constexpr (R <= 2) {
+                // two or three users, an even number of columns >= 128: the packed walk of walk_f64.hpp (round 6; complex64 since its last day)
+                if (kc && link_walk_f64_fits(cfg->n_symbols) && !ctx->opt[MCLE_OPT_WALK_LEGACY]) {
 #define MCLE_BD_PACKED(KC_, ABL_)                                                                                             \
-    if (!walked && cfg->K == KC_) {                                                                                           \
-        launch_link_walk<T, BdWalk<KC_, R>, ABL_>(ctx, mp, cfg->n_symbols, pp.noise_var, seed, first + off, m, (const cx<T>*)recs, \
-                                                   d_counters, d_sym_err ? d_sym_err + off : nullptr,                        \
-                                                   d_bit_err ? d_bit_err + off : nullptr);                                   \
-        walked = true;                                                                                                        \
+    if (cfg->K == KC_) {                                                                                                      \
+        launch_link_walk<T, BdWalk<KC_, R>, ABL_>(ctx, mp, cfg->n_symbols, pp.noise_var, seed, at, m, (const cx<T>*)recs,     \
+                                                   d_counters, sym, bit);                                                    \
+        return;                                                                                                               \
     }
 #ifdef MCLE_EXPERIMENTS
-                if constexpr (R == 2 && sizeof(T) == 8) {
-                    switch ((int)ctx->opt[MCLE_OPT_F64_VARIANT]) {
-                        case 1: MCLE_BD_PACKED(3, 1) break;
-                        case 2: MCLE_BD_PACKED(3, 2) break;
-                        case 4: MCLE_BD_PACKED(3, 4) break;
-                        case 6: MCLE_BD_PACKED(3, 6) break;
-                        case 8: MCLE_BD_PACKED(3, 8) break;
-                        case 16: MCLE_BD_PACKED(3, 16) break;
-                        case 31: MCLE_BD_PACKED(3, 31) break;
-                        default: break;
+                    if constexpr (R == 2 && sizeof(T) == 8) {
+                        switch ((int)ctx->opt[MCLE_OPT_F64_VARIANT]) {
+                            case 1: MCLE_BD_PACKED(3, 1) break;
+                            case 2: MCLE_BD_PACKED(3, 2) break;
+                            case 4: MCLE_BD_PACKED(3, 4) break;
+                            case 6: MCLE_BD_PACKED(3, 6) break;
+                            case 8: MCLE_BD_PACKED(3, 8) break;
+                            case 16: MCLE_BD_PACKED(3, 16) break;
+                            case 31: MCLE_BD_PACKED(3, 31) break;
+                            default: break;
+                        }
                     }
-                }
 #endif
-                MCLE_BD_PACKED(2, 0) MCLE_BD_PACKED(3, 0)
+                    MCLE_BD_PACKED(2, 0) MCLE_BD_PACKED(3, 0)
 #undef MCLE_BD_PACKED
+                }
             }
-        }
-        if constexpr (R <= 2) {                    // users as a compile-time count where the arrays then shrink: K = 2, 3
-            MCLE_BD_WALK(2, 0) MCLE_BD_WALK(2, 1) MCLE_BD_WALK(2, 2) MCLE_BD_WALK(3, 0) MCLE_BD_WALK(3, 1) MCLE_BD_WALK(3, 2)
-        }
-        MCLE_BD_WALK(0, 0) MCLE_BD_WALK(0, 1) MCLE_BD_WALK(0, 2)
-#undef MCLE_BD_WALK
-        MCLE_LAUNCH_CHECK();
+            // the resident set: the wavefronts per SIMD of k_bd_link's __launch_bounds__ (3 for complex64 and the compile-time user
+            // counts, 2 otherwise) -- rounds 4-5 sized the complex64 grid for four and ran a partial second wave of workgroups
+            // (a chunk is 8-16 realizations; one chunk per workgroup measured 1.5 x slower)
+            const unsigned grid = walk_grid(ctx, (sizeof(T) == 4 || kc) ? 3 : 2, m, per_wave, 2);
+#define MCLE_BD_WALK(KC_, MODE_)                                                                                          \
+    if ((KC_ == 0 || (cfg->K == KC_ && KC_ * R <= kBdMaxN)) && mode == MODE_) {                                             \
+        hipLaunchKernelGGL((k_bd_link<T, R, (KC_ * R <= kBdMaxN ? KC_ : 0), (sizeof(T) == 4 ? MODE_ : 0)>), dim3(grid), dim3(256), lds, \
+                           ctx->stream, mp, pp, seed, at, m, per_wave, (const cx<T>*)recs, d_counters, sym, bit);          \
+        return;                                                                                                           \
     }
-    return MCLE_OK;
+            if constexpr (R <= 2) {                    // users as a compile-time count where the arrays then shrink: K = 2, 3
+                MCLE_BD_WALK(2, 0) MCLE_BD_WALK(2, 1) MCLE_BD_WALK(2, 2) MCLE_BD_WALK(3, 0) MCLE_BD_WALK(3, 1) MCLE_BD_WALK(3, 2)
+            }
+            MCLE_BD_WALK(0, 0) MCLE_BD_WALK(0, 1) MCLE_BD_WALK(0, 2)
+#undef MCLE_BD_WALK
+        });
 }
 
 static int check_bd_dims(int K, int r) {
@@ -556,7 +537,7 @@ int mcle_run_bd(mcle_ctx* ctx, int dtype, const mcle_bd_cfg* cfg, uint64_t seed,
     MCLE_REQUIRE(cfg->n_symbols >= 1, "n_symbols must be positive");
     MCLE_REQUIRE(cfg->iPu > 0.0, "the power per user must be positive");
     MCLE_REQUIRE(cfg->noise_var >= 0.0 && cfg->bd_noise_var >= 0.0, "noise variances must be non-negative");
-    MCLE_REQUIRE(count <= 0x7fffffffull, "at most 2^31-1 realizations per call");
+    if ((rc = check_link_draws((uint64_t)(cfg->K * cfg->nr), cfg->n_symbols, count))) return rc;
     BdParams pp;
     pp.K = cfg->K;
     pp.r = cfg->nr;

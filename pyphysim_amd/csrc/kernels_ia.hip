@@ -17,6 +17,7 @@
 #include "qam_pack.hpp"
 #include "wave_draws.hpp"
 #include "walk_f64.hpp"
+#include "link_walk.hpp"
 #include "quant.hpp"
 
 namespace mcle {
@@ -606,24 +607,12 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? MCLE_F32_WALK_WAVES : 3) void
     __shared__ float4 s_tab4[sizeof(T) == 4 ? 256 : 1];     // {re, im, |c|^2 / 2, 0}: the lockstep searches of modem.hpp
     extern __shared__ unsigned long long s_grid[];       // [G*G] candidate grid (min-distance demodulation, f32)
     __shared__ double s_bm[sizeof(T) == 8 ? kBmLdsDoubles : 1];   // complex128 Box-Muller tables (bm_f64.hpp)
-    if constexpr (sizeof(T) == 8) bm_tables_to_lds(s_bm, (int)threadIdx.x, (int)blockDim.x);
-    load_table(mp, s_table);
-    load_grid(mp, s_grid);
-    if constexpr (sizeof(T) == 4)
-        for (int m = threadIdx.x; m < mp.M; m += blockDim.x) {
-            const float2 c = mp.g_table[m];
-            s_tab4[m] = make_float4(c.x, c.y, 0.5f * (c.x * c.x + c.y * c.y), 0.f);
-        }
-    const bool lockstep = sizeof(T) == 4 && mp.method == MCLE_DEMOD_MINDIST && (mp.M <= 8 || mp.grid.G > 0);
+    link_prologue(mp, s_table, s_tab4, s_grid, s_bm);
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const T sigma = (T)sqrt(noise_var);
     const uint32_t mask = (uint32_t)(mp.M - 1);
-    const bool packed = sizeof(T) == 4 && mp.method == MCLE_DEMOD_QAM_SLICER;
-    QamPack qp{};
-    if constexpr (sizeof(T) == 4) {
-        if (packed) qp = qam_pack(mp);
-    }
+    const LinkDecide<T> w = link_decide_for(mp, s_table, s_tab4, s_grid, 3);
     __shared__ WgTotals totals_all[4];
     WgTotals& totals = totals_all[wv];
     if (lane == 0) wg_zero(totals);
@@ -655,33 +644,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? MCLE_F32_WALK_WAVES : 3) void
 #pragma unroll
                     for (int l = 0; l < 3; ++l) est[k] = cfma4(G[k][l], x[l], est[k]);
                 }
-                if constexpr (sizeof(T) == 4) {
-                    if (packed) {   // the three decisions of the column in one packed level-domain slice (qam_pack.hpp)
-                        const f4q er = {est[0].x, est[1].x, est[2].x, 0.f}, ei = {est[0].y, est[1].y, est[2].y, 0.f};
-                        const uint32_t sent = (uint32_t)tx[0] | ((uint32_t)tx[1] << 8) | ((uint32_t)tx[2] << 16);
-                        qam_count4((qam_levels4(er, ei, qp) ^ labels_to_levels(sent, qp)) & 0x00FFFFFFu, qp, se, be);
-                        return;
-                    }
-                }
-                int dec[3];
-                bool done = false;
-                if constexpr (sizeof(T) == 4) {
-                    if (lockstep) {       // the three streams searched in lockstep (same decisions as demod_one)
-                        if (mp.M <= 8) demod_multi_cert(mp, est, dec, [&](int (&d_)[3]) { demod_mindist_multi<3>(s_tab4, mp.M, est, d_); });
-                        else demod_multi_cert(mp, est, dec, [&](int (&d_)[3]) { demod_grid4_multi<3>(s_tab4, s_grid, mp.grid, mp.M, est, d_); });
-                        done = true;
-                    }
-                }
-                if (!done) {
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) dec[k] = demod_one(mp, s_table, s_grid, est[k]);
-                }
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const unsigned e = (unsigned)(tx[k] ^ dec[k]);
-                    se += (e != 0u);
-                    be += __popc(e);
-                }
+                link_decide<T, 3>(w, est, tx, se, be);
             };
             if ((n_symbols & 1) == 0) {
                 for (int t0 = 0; t0 < n_symbols; t0 += kPairCols) {
@@ -741,9 +704,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? MCLE_F32_WALK_WAVES : 3) void
                     column(tx, nz);
                 }
             }
-            se = wave_sum_u32(se);
-            be = wave_sum_u32(be);
-            if (lane == 0) wg_account(totals, se, be, !ok, rl, sym_out, bit_out);
+            link_account(totals, se, be, !ok, rl, lane, sym_out, bit_out);
         }
     }
     wg_flush_waves<4>(totals_all, counters, 3ull * (unsigned long long)n_symbols, 3ull * (unsigned long long)n_symbols * mp.bits);
@@ -763,66 +724,55 @@ template <typename T>
 int run_ia_impl(mcle_ctx* ctx, const mcle_ia_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
                 mcle_counters* d_counters, uint32_t* d_sym, uint32_t* d_bit, double* d_cap, uint32_t* d_iter,
                 const IaQuantRun* qr = nullptr) {
-    int rc;
-    void* recs = nullptr;
-    const uint64_t slice = count < kSolveSlice ? count : kSolveSlice;
     // quantized: the slice's chosen distances [slice][9] (double) and indices [slice][9] (int32) follow the records
-    const size_t rec_bytes = (size_t)slice * kIaRec * sizeof(cx<T>);
-    if ((rc = ctx->scratch(rec_bytes + (qr ? (size_t)slice * 9 * (sizeof(double) + sizeof(int32_t)) : 0), &recs))) return rc;
-    double* q_dist = reinterpret_cast<double*>(static_cast<char*>(recs) + rec_bytes);
-    int32_t* q_index = reinterpret_cast<int32_t*>(q_dist + slice * 9);
+    const uint64_t slice = count < kSolveSlice ? count : kSolveSlice;
     const ModemParams<T> mp = pipe_modem<T>(ctx, cfg->demod_method);
     const size_t lds = (size_t)mp.grid.G * mp.grid.G * sizeof(unsigned long long);
     const int per_wave = 16;      // 4 ... 64 realizations per wavefront measured: 1.98-2.05e8 realizations/s, no trend
-    for (uint64_t off = 0; off < count; off += slice) {
-        const uint64_t n = count - off < slice ? count - off : slice;
-        if (qr) {
-            int32_t* idx = qr->d_index ? qr->d_index + off * 9 : q_index;
-            if ((rc = launch_quantize_drawn(ctx, sizeof(T) == 8 ? MCLE_F64 : MCLE_F32, qr->qcfg, qr->d_codebook, seed, first + off, n,
-                                            idx, q_dist)))
-                return rc;
-            IaQuantSrc<T, true> q;
-            q.codebook = (const cx<T>*)qr->d_codebook, q.index = idx, q.dist = q_dist;
-            q.dist_sum = qr->d_dist_sum ? qr->d_dist_sum + off : nullptr;
-            auto solve = cfg->solver == IA_CLOSED_FORM ? k_ia_solve_links<T, false, true> : k_ia_solve_links<T, true, true>;
-            hipLaunchKernelGGL(solve, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, cfg->noise_var,
-                               cfg->solver, cfg->initialize_with, cfg->max_iterations, cfg->relative_factor, seed, first + off, n,
-                               (cx<T>*)recs, d_cap ? d_cap + off : nullptr, d_iter ? d_iter + off : nullptr, q);
-        } else {
-            auto solve = cfg->solver == IA_CLOSED_FORM ? k_ia_solve_links<T, false> : k_ia_solve_links<T, true>;
-            hipLaunchKernelGGL(solve, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, cfg->noise_var,
-                               cfg->solver, cfg->initialize_with, cfg->max_iterations, cfg->relative_factor, seed, first + off, n,
-                               (cx<T>*)recs, d_cap ? d_cap + off : nullptr, d_iter ? d_iter + off : nullptr,
-                               IaQuantSrc<T, false>{});
-        }
-        MCLE_LAUNCH_CHECK();
-        const uint64_t chunks = (n + per_wave - 1) / per_wave;
-        const uint64_t cap = (uint64_t)ctx->n_cu * (sizeof(T) == 4 ? 4 : 3);                    // workgroups of four wavefronts
-        const unsigned grid = (unsigned)oversubscribed_grid(ctx, cap, (chunks + 3) / 4, 2);     // a chunk is 8-16 realizations; one chunk per workgroup measured 1.5 x slower
-        bool walked = false;
-        {
+    return launch_sliced(
+        ctx, first, count, kSolveSlice, kIaRec * sizeof(cx<T>), d_sym, d_bit,
+        [&](void* recs, uint64_t at, uint64_t n) -> int {
+            const uint64_t off = at - first;
+            if (qr) {
+                double* q_dist = reinterpret_cast<double*>(static_cast<char*>(recs) + (size_t)slice * kIaRec * sizeof(cx<T>));
+                int32_t* q_index = reinterpret_cast<int32_t*>(q_dist + slice * 9);
+                int32_t* idx = qr->d_index ? qr->d_index + off * 9 : q_index;
+                if (int rc = launch_quantize_drawn(ctx, sizeof(T) == 8 ? MCLE_F64 : MCLE_F32, qr->qcfg, qr->d_codebook, seed, at, n, idx,
+                                                   q_dist))
+                    return rc;
+                IaQuantSrc<T, true> q;
+                q.codebook = (const cx<T>*)qr->d_codebook, q.index = idx, q.dist = q_dist;
+                q.dist_sum = qr->d_dist_sum ? qr->d_dist_sum + off : nullptr;
+                auto solve = cfg->solver == IA_CLOSED_FORM ? k_ia_solve_links<T, false, true> : k_ia_solve_links<T, true, true>;
+                hipLaunchKernelGGL(solve, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, cfg->noise_var, cfg->solver,
+                                   cfg->initialize_with, cfg->max_iterations, cfg->relative_factor, seed, at, n, (cx<T>*)recs,
+                                   d_cap ? d_cap + off : nullptr, d_iter ? d_iter + off : nullptr, q);
+            } else {
+                auto solve = cfg->solver == IA_CLOSED_FORM ? k_ia_solve_links<T, false> : k_ia_solve_links<T, true>;
+                hipLaunchKernelGGL(solve, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, cfg->noise_var, cfg->solver,
+                                   cfg->initialize_with, cfg->max_iterations, cfg->relative_factor, seed, at, n, (cx<T>*)recs,
+                                   d_cap ? d_cap + off : nullptr, d_iter ? d_iter + off : nullptr, IaQuantSrc<T, false>{});
+            }
+            return MCLE_OK;
+        },
+        [&](void* recs, uint64_t at, uint64_t n, uint32_t* sym, uint32_t* bit) {
             // an even number of columns >= 128: the packed walk of walk_f64.hpp (round 6; complex64 since its last day)
             if (link_walk_f64_fits(cfg->n_symbols) && !ctx->opt[MCLE_OPT_WALK_LEGACY]) {
 #ifdef MCLE_EXPERIMENTS
-              if constexpr (sizeof(T) == 8) {
-#define MCLE_IA_ABL(V_) case V_: launch_link_walk_f64<IaWalk, V_>(ctx, mp, cfg->n_symbols, cfg->noise_var, seed, first + off, n, (const double2*)recs, d_counters, d_sym ? d_sym + off : nullptr, d_bit ? d_bit + off : nullptr); walked = true; break;
-                switch ((int)ctx->opt[MCLE_OPT_F64_VARIANT]) { MCLE_IA_ABL(1) MCLE_IA_ABL(2) MCLE_IA_ABL(4) MCLE_IA_ABL(6) MCLE_IA_ABL(8) MCLE_IA_ABL(16) MCLE_IA_ABL(31) default: break; }
+                if constexpr (sizeof(T) == 8) {
+#define MCLE_IA_ABL(V_) case V_: launch_link_walk_f64<IaWalk, V_>(ctx, mp, cfg->n_symbols, cfg->noise_var, seed, at, n, (const double2*)recs, d_counters, sym, bit); return;
+                    switch ((int)ctx->opt[MCLE_OPT_F64_VARIANT]) { MCLE_IA_ABL(1) MCLE_IA_ABL(2) MCLE_IA_ABL(4) MCLE_IA_ABL(6) MCLE_IA_ABL(8) MCLE_IA_ABL(16) MCLE_IA_ABL(31) default: break; }
 #undef MCLE_IA_ABL
-              }
+                }
 #endif
-                if (!walked)
-                    launch_link_walk<T, IaWalk>(ctx, mp, cfg->n_symbols, cfg->noise_var, seed, first + off, n, (const cx<T>*)recs,
-                                                d_counters, d_sym ? d_sym + off : nullptr, d_bit ? d_bit + off : nullptr);
-                walked = true;
+                launch_link_walk<T, IaWalk>(ctx, mp, cfg->n_symbols, cfg->noise_var, seed, at, n, (const cx<T>*)recs, d_counters, sym, bit);
+                return;
             }
-        }
-        if (!walked)
-            hipLaunchKernelGGL(k_ia_link<T>, dim3(grid), dim3(256), lds, ctx->stream, mp, cfg->n_symbols, cfg->noise_var, seed,
-                               first + off, n, per_wave, (const cx<T>*)recs, d_counters, d_sym ? d_sym + off : nullptr,
-                               d_bit ? d_bit + off : nullptr);
-        MCLE_LAUNCH_CHECK();
-    }
-    return MCLE_OK;
+            // (a chunk is 8-16 realizations; one chunk per workgroup measured 1.5 x slower)
+            hipLaunchKernelGGL(k_ia_link<T>, dim3(walk_grid(ctx, sizeof(T) == 4 ? 4 : 3, n, per_wave, 2)), dim3(256), lds, ctx->stream, mp,
+                               cfg->n_symbols, cfg->noise_var, seed, at, n, per_wave, (const cx<T>*)recs, d_counters, sym, bit);
+        },
+        qr ? 9 * (sizeof(double) + sizeof(int32_t)) : 0);
 }
 
 }  // namespace mcle
@@ -921,6 +871,5 @@ static int check_run_ia(mcle_ctx* ctx, int dtype, const mcle_ia_cfg* cfg, uint64
                  "unknown initialisation %d", cfg->initialize_with);
     MCLE_REQUIRE(!(cfg->solver == MCLE_IA_ALT_MIN && cfg->initialize_with == MCLE_IA_INIT_ALT_MIN),
                  "Can't use 'alt_min' initialization with 'AlternatingMinIASolver' class 'alt_min'");
-    MCLE_REQUIRE(count <= 0x7fffffffull, "at most 2^31-1 realizations per call");
-    return MCLE_OK;
+    return check_link_draws(6, cfg->n_symbols, count);      // six receive antennas' noise rows, three data rows
 }

@@ -638,4 +638,15 @@ __device__ __forceinline__ void load_table(const ModemParams<T>& mp, cx<T>* s_ta
     for (int m = threadIdx.x; m < mp.M; m += blockDim.x) s_table[m] = mp.g_table[m];
 }
 
+// the complex64 table of the lockstep searches, {re, im, |c|^2 / 2, 0}, from the launch's constellation: a complex128 table gives
+// the half norm in double before the cast
+template <typename T>
+__device__ __forceinline__ void load_tab4(const ModemParams<T>& mp, float4* s_tab4) {
+    for (int m = threadIdx.x; m < mp.M; m += blockDim.x) {
+        const cx<T> c = mp.g_table[m];
+        if constexpr (sizeof(T) == 4) s_tab4[m] = make_float4(c.x, c.y, 0.5f * (c.x * c.x + c.y * c.y), 0.f);
+        else s_tab4[m] = make_float4((float)c.x, (float)c.y, (float)(0.5 * (c.x * c.x + c.y * c.y)), 0.f);
+    }
+}
+
 }  // namespace mcle

@@ -152,6 +152,16 @@ __device__ __forceinline__ void cn_pair_lds(const Rng& rng, uint32_t stream, uin
     z1 = cn_from_words_lds(b.w[2], b.w[3], sigma, s_bm);
 }
 
+// one complex normal of `stream` against the caller's LDS copy of the complex128 tables (complex64 has none)
+__device__ __forceinline__ float2 cn_one_lds(const Rng& rng, uint32_t stream, uint32_t i, float sigma, const double*) {
+    return cn_sample<float>(rng, stream, i, sigma);
+}
+__device__ __forceinline__ double2 cn_one_lds(const Rng& rng, uint32_t stream, uint32_t i, double sigma, const double* s_bm) {
+    const Words4 b = rng.block(stream, i >> 1);
+    const bool hi = (i & 1) != 0;
+    return cn_from_words_lds(hi ? b.w[2] : b.w[0], hi ? b.w[3] : b.w[1], sigma, s_bm);
+}
+
 __device__ __forceinline__ double uniform_at(const Rng& rng, uint32_t stream, uint64_t i) {
     const Words4 b = rng.block(stream, (uint32_t)(i >> 2));
     const uint32_t lo = (i & 1) ? b.w[1] : b.w[0], hi = (i & 1) ? b.w[3] : b.w[2];      // (selects: see cn_sample)

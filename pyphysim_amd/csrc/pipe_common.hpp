@@ -3,6 +3,7 @@
 #include "common.hpp"
 #include "modem.hpp"
 #include "c4_select.hpp"
+#include <type_traits>
 
 namespace mcle {
 
@@ -62,21 +63,49 @@ inline uint64_t flush_min_units(uint64_t base, uint64_t k_samples, uint64_t samp
     return m > base ? m : base;
 }
 
+// Grid of a walk by workgroups of four independent wavefronts, a wavefront taking chunks of per_wave realizations: the resident
+// set is wgs_per_cu workgroups per CU (the kernel's wavefronts per SIMD), a unit of oversubscribed_grid is one workgroup's four chunks.
+inline unsigned walk_grid(const mcle_ctx* ctx, uint64_t wgs_per_cu, uint64_t n, int per_wave, uint64_t min_units = 8) {
+    const uint64_t chunks = (n + per_wave - 1) / per_wave;
+    return (unsigned)oversubscribed_grid(ctx, (uint64_t)ctx->n_cu * wgs_per_cu, (chunks + 3) / 4, min_units);
+}
+
+// a launch callback may return void or an mcle status
+template <typename F, typename... A> inline int launch_step(F&& f, A&&... a) {
+    if constexpr (std::is_void_v<decltype(f(a...))>) {
+        f(a...);
+        return MCLE_OK;
+    } else {
+        return f(a...);
+    }
+}
+
 // A launch in slices of at most k_slice realizations, so that the record buffer (rec_bytes per realization, the context's scratch)
 // stays bounded: per slice records(recs, first, n) starts the kernel that writes the slice's records and link(recs, first, n, sym, bit)
-// the kernel that walks them; sym / bit: the per-realization outputs at the slice (or null).
+// the kernel that walks them; sym / bit: the per-realization outputs at the slice (or null).  A launcher that bounds the buffer in
+// bytes passes k_slice = bytes / rec_bytes.
+// tail_bytes: further per-realization scratch of the slice (flag words, indices); its arrays follow the records, at
+// recs + slice * rec_bytes with slice = min(count, k_slice).
+// floor > 0: on a crowded device the slice may shrink down to `floor` realizations (scratch_upto) instead of the call failing; not
+// combined with a tail, whose place depends on the slice.
 template <typename Records, typename Link>
 inline int launch_sliced(mcle_ctx* ctx, uint64_t first, uint64_t count, uint64_t k_slice, size_t rec_bytes, uint32_t* d_sym,
-                         uint32_t* d_bit, Records&& records, Link&& link) {
-    const uint64_t slice = count < k_slice ? count : k_slice;
+                         uint32_t* d_bit, Records&& records, Link&& link, size_t tail_bytes = 0, uint64_t floor = 0) {
+    uint64_t slice = count < k_slice ? count : k_slice;
     void* recs = nullptr;
     int rc;
-    if ((rc = ctx->scratch((size_t)slice * rec_bytes, &recs))) return rc;
+    if (floor > 0) {
+        size_t got = 0;
+        if ((rc = ctx->scratch_upto((size_t)slice * rec_bytes, (size_t)(slice < floor ? slice : floor) * rec_bytes, &recs, &got))) return rc;
+        if (got / rec_bytes < slice) slice = got / rec_bytes;
+    } else if ((rc = ctx->scratch((size_t)slice * (rec_bytes + tail_bytes), &recs))) {
+        return rc;
+    }
     for (uint64_t off = 0; off < count; off += slice) {
         const uint64_t n = count - off < slice ? count - off : slice;
-        records(recs, first + off, n);
+        if ((rc = launch_step(records, recs, first + off, n))) return rc;
         MCLE_LAUNCH_CHECK();
-        link(recs, first + off, n, d_sym ? d_sym + off : nullptr, d_bit ? d_bit + off : nullptr);
+        if ((rc = launch_step(link, recs, first + off, n, d_sym ? d_sym + off : nullptr, d_bit ? d_bit + off : nullptr))) return rc;
         MCLE_LAUNCH_CHECK();
     }
     return MCLE_OK;
@@ -102,6 +131,14 @@ template <typename T> ModemParams<T> pipe_modem(const mcle_ctx* ctx, int method)
     p.half_bits = ctx->bits / 2;
     modem_fill_cert(ctx, method, p);
     return p;
+}
+
+// The draw rules of the record-walking links: a realization index and a draw position are 32-bit in their kernels.  rows: the
+// larger of the kernel's noise rows and data rows (a position is row * n_symbols + column).
+inline int check_link_draws(uint64_t rows, int n_symbols, uint64_t count) {
+    MCLE_REQUIRE(rows * (uint64_t)n_symbols <= 0x7fffffffull, "n_symbols too large: draw positions are 32-bit");
+    MCLE_REQUIRE(count <= 0x7fffffffull, "at most 2^31-1 realizations per call");
+    return MCLE_OK;
 }
 
 inline int check_pipe(const mcle_ctx* ctx, int dtype, int method, const void* cfg) {

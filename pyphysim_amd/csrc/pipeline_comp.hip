@@ -25,6 +25,7 @@
 #include "pipe_common.hpp"
 #include "totals.hpp"
 #include "wave_draws.hpp"
+#include "link_walk.hpp"
 #include "bd_extint.hpp"
 
 namespace mcle {
@@ -155,17 +156,6 @@ __global__ __launch_bounds__(64) void k_comp_solve_links(CompParams pp, uint64_t
     rec[n * (1 + R + E)] = mk<T>(ok ? (T)1 : (T)0, (T)0);
 }
 
-// one complex normal of `stream` against the caller's LDS copy of the complex128 tables (complex64 has none)
-__device__ __forceinline__ float2 comp_cn_one(const Rng& rng, uint32_t stream, uint32_t i, float sigma, const double*) {
-    return cn_sample<float>(rng, stream, i, sigma);
-}
-__device__ __forceinline__ double2 comp_cn_one(const Rng& rng, uint32_t stream, uint32_t i, double sigma,
-                                               const double* s_bm) {
-    const Words4 b = rng.block(stream, i >> 1);
-    const bool hi = (i & 1) != 0;
-    return cn_from_words_lds(hi ? b.w[2] : b.w[0], hi ? b.w[3] : b.w[1], sigma, s_bm);
-}
-
 // The symbol walk: workgroups of four independent wavefronts, each taking chunks of per_wave realizations; the lanes
 // of a wavefront take the symbol columns of one realization -- two adjacent columns each where n_symbols is even (the
 // two samples of one Philox block per noise / interferer draw, the data blocks shared across the wave), one otherwise.
@@ -188,9 +178,7 @@ __global__ __launch_bounds__(256) void k_comp_link(ModemParams<T> mp, CompParams
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     WgTotals& totals = totals_all[wv];
     __shared__ double s_bm[sizeof(T) == 8 ? kBmLdsDoubles : 1];   // complex128 Box-Muller tables (bm_f64.hpp)
-    if constexpr (sizeof(T) == 8) bm_tables_to_lds(s_bm, (int)threadIdx.x, (int)blockDim.x);
-    load_table(mp, s_table);
-    load_grid(mp, s_grid);
+    link_prologue(mp, s_table, nullptr, s_grid, s_bm);     // (no lockstep table: demod_one per stream)
     const int lane = threadIdx.x & 63;
     const T sigma = (T)sqrt(pp.noise_var);
     const uint32_t mask = (uint32_t)(mp.M - 1);
@@ -228,7 +216,7 @@ __global__ __launch_bounds__(256) void k_comp_link(ModemParams<T> mp, CompParams
                         if constexpr (PAIR)
                             cn_pair_lds(rng, STREAM_PHASE, ((uint32_t)e * NS + t) >> 1, (T)1, ze[0][e], ze[COLS - 1][e], s_bm);
                         else
-                            ze[0][e] = comp_cn_one(rng, STREAM_PHASE, (uint32_t)e * NS + t, (T)1, s_bm);
+                            ze[0][e] = cn_one_lds(rng, STREAM_PHASE, (uint32_t)e * NS + t, (T)1, s_bm);
                     }
                 int q0 = 0;                          // active streams before this user
 #pragma unroll
@@ -242,7 +230,7 @@ __global__ __launch_bounds__(256) void k_comp_link(ModemParams<T> mp, CompParams
                                 cn_pair_lds(rng, STREAM_NOISE, ((uint32_t)(k * R + a) * NS + t) >> 1, sigma, nz[0][a],
                                             nz[COLS - 1][a], s_bm);
                             else
-                                nz[0][a] = comp_cn_one(rng, STREAM_NOISE, (uint32_t)(k * R + a) * NS + t, sigma, s_bm);
+                                nz[0][a] = cn_one_lds(rng, STREAM_NOISE, (uint32_t)(k * R + a) * NS + t, sigma, s_bm);
                         }
 #pragma unroll
                         for (int jj = 0; jj < R; ++jj)
@@ -303,36 +291,32 @@ static int launch_run_comp(mcle_ctx* ctx, const mcle_comp_cfg* cfg, const CompPa
                            double* d_sinr) {
     const int K = cfg->K, n = K * R, E = cfg->n_ext;
     const ModemParams<T> mp = pipe_modem<T>(ctx, cfg->demod_method);
-    int rc;
-    void* recs = nullptr;
     const uint64_t kSlice = 1ull << 18;          // realizations per solve + walk pair: bounds the record buffer
-    const uint64_t slice = count < kSlice ? count : kSlice;
     const size_t stride = (size_t)(n * (1 + R + E) + 1 + K);
-    if ((rc = ctx->scratch((size_t)slice * stride * sizeof(cx<T>), &recs))) return rc;
     const size_t lds = (size_t)mp.grid.G * mp.grid.G * sizeof(unsigned long long);
     const int per_wave = 8;
     const bool pair = (cfg->n_symbols & 1) == 0;
-    for (uint64_t off = 0; off < count; off += slice) {
-        const uint64_t m = count - off < slice ? count - off : slice;
-        hipLaunchKernelGGL((k_comp_solve_links<T, R>), dim3((unsigned)((m + 63) / 64)), dim3(64), 0, ctx->stream, pp, seed,
-                           first + off, m, d_pathloss ? d_pathloss + off * (size_t)K * (K + E) : nullptr, (cx<T>*)recs,
-                           d_ns ? d_ns + off * K : nullptr, d_sinr ? d_sinr + off * n : nullptr);
-        MCLE_LAUNCH_CHECK();
-        const uint64_t cap = (uint64_t)ctx->n_cu * 2;                                    // workgroups of four wavefronts
-        const uint64_t chunks = (m + per_wave - 1) / per_wave;
-        const unsigned grid = (unsigned)oversubscribed_grid(ctx, cap, (chunks + 3) / 4, 2);
-        uint32_t* se = d_sym_err ? d_sym_err + off : nullptr;
-        uint32_t* be = d_bit_err ? d_bit_err + off : nullptr;
-        uint32_t* sse = d_stream_sym_err ? d_stream_sym_err + off * n : nullptr;
-        uint32_t* sbe = d_stream_bit_err ? d_stream_bit_err + off * n : nullptr;
-        if (pair)
-            hipLaunchKernelGGL((k_comp_link<T, R, true>), dim3(grid), dim3(256), lds, ctx->stream, mp, pp, seed, first + off, m,
-                               per_wave, (const cx<T>*)recs, d_counters, se, be, sse, sbe);
-        else
-            hipLaunchKernelGGL((k_comp_link<T, R, false>), dim3(grid), dim3(256), lds, ctx->stream, mp, pp, seed, first + off, m,
-                               per_wave, (const cx<T>*)recs, d_counters, se, be, sse, sbe);
-        MCLE_LAUNCH_CHECK();
-    }
+    const int rc = launch_sliced(
+        ctx, first, count, kSlice, stride * sizeof(cx<T>), d_sym_err, d_bit_err,
+        [&](void* recs, uint64_t at, uint64_t m) {
+            const uint64_t off = at - first;
+            hipLaunchKernelGGL((k_comp_solve_links<T, R>), dim3((unsigned)((m + 63) / 64)), dim3(64), 0, ctx->stream, pp, seed, at, m,
+                               d_pathloss ? d_pathloss + off * (size_t)K * (K + E) : nullptr, (cx<T>*)recs,
+                               d_ns ? d_ns + off * K : nullptr, d_sinr ? d_sinr + off * n : nullptr);
+        },
+        [&](void* recs, uint64_t at, uint64_t m, uint32_t* se, uint32_t* be) {
+            const uint64_t off = at - first;
+            const unsigned grid = walk_grid(ctx, 2, m, per_wave, 2);
+            uint32_t* sse = d_stream_sym_err ? d_stream_sym_err + off * n : nullptr;
+            uint32_t* sbe = d_stream_bit_err ? d_stream_bit_err + off * n : nullptr;
+            if (pair)
+                hipLaunchKernelGGL((k_comp_link<T, R, true>), dim3(grid), dim3(256), lds, ctx->stream, mp, pp, seed, at, m, per_wave,
+                                   (const cx<T>*)recs, d_counters, se, be, sse, sbe);
+            else
+                hipLaunchKernelGGL((k_comp_link<T, R, false>), dim3(grid), dim3(256), lds, ctx->stream, mp, pp, seed, at, m, per_wave,
+                                   (const cx<T>*)recs, d_counters, se, be, sse, sbe);
+        });
+    if (rc) return rc;
     ctx->set_kernel("comp_link %s r%d %s", sizeof(T) == 8 ? "f64" : "f32", R, pair ? "pairs" : "single");
     return MCLE_OK;
 }
@@ -364,10 +348,8 @@ int mcle_run_comp(mcle_ctx* ctx, int dtype, const mcle_comp_cfg* cfg, uint64_t s
         MCLE_REQUIRE(cfg->num_streams >= 1 && cfg->num_streams <= cfg->r, "num_streams must be in [1, %d]", cfg->r);
     if (cfg->method == 1 && cfg->metric == 4)
         MCLE_REQUIRE(cfg->packet_length >= 1, "packet_length must be positive");
-    MCLE_REQUIRE(count <= 0x7fffffffull, "at most 2^31-1 realizations per call");
-    MCLE_REQUIRE((uint64_t)cfg->K * cfg->r * (uint64_t)cfg->n_symbols <= 0x7fffffffull &&
-                     (uint64_t)cfg->n_ext * (uint64_t)cfg->n_symbols <= 0x7fffffffull,
-                 "n_symbols too large: draw positions are 32-bit");
+    // rows: the users' K r antennas (noise, data), the interferers' n_ext antennas (their symbols)
+    if ((rc = check_link_draws((uint64_t)(cfg->K * cfg->r > cfg->n_ext ? cfg->K * cfg->r : cfg->n_ext), cfg->n_symbols, count))) return rc;
     CompParams pp;
     pp.K = cfg->K;
     pp.r = cfg->r;

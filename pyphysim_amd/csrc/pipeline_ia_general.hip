@@ -22,6 +22,7 @@
 #include "pipe_common.hpp"
 #include "totals.hpp"
 #include "wave_draws.hpp"
+#include "link_walk.hpp"
 #include "ia_general.hpp"
 
 namespace mcle {
@@ -124,16 +125,6 @@ __global__ __launch_bounds__(64) void k_iagl_record(IaglShape sh, const double2*
         }
 }
 
-// one complex normal of `stream` against the caller's LDS copy of the complex128 tables (complex64 has none)
-__device__ __forceinline__ float2 iagl_cn_one(const Rng& rng, uint32_t stream, uint32_t i, float sigma, const double*) {
-    return cn_sample<float>(rng, stream, i, sigma);
-}
-__device__ __forceinline__ double2 iagl_cn_one(const Rng& rng, uint32_t stream, uint32_t i, double sigma, const double* s_bm) {
-    const Words4 b = rng.block(stream, i >> 1);
-    const bool hi = (i & 1) != 0;
-    return cn_from_words_lds(hi ? b.w[2] : b.w[0], hi ? b.w[3] : b.w[1], sigma, s_bm);
-}
-
 // The symbol walk: workgroups of four independent wavefronts, each taking chunks of per_wave consecutive realizations; the
 // lanes of a wavefront take the symbol columns of one realization -- two adjacent columns each where n_symbols is even (PAIR:
 // the two samples of one Philox block per noise draw, the data blocks shared across the wave), one otherwise.
@@ -162,9 +153,7 @@ __global__ __launch_bounds__(256) void k_iagl_link(ModemParams<T> mp, IaglShape 
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     WgTotals& totals = totals_all[wv];
     unsigned(&s_cnt)[2][SLOTS] = s_cnt_all[wv];
-    if constexpr (sizeof(T) == 8) bm_tables_to_lds(s_bm, (int)threadIdx.x, (int)blockDim.x);
-    load_table(mp, s_table);
-    load_grid(mp, s_grid);
+    link_prologue(mp, s_table, nullptr, s_grid, s_bm);     // (no lockstep table: demod_one per stream)
     const int lane = threadIdx.x & 63;
     const int K = sh.K, nr = sh.nr, S0 = sh.S0;
     const int stride = 1 + S0 * S0 + S0 * nr, stride_lds = (stride + 1) & ~1;
@@ -233,7 +222,7 @@ __global__ __launch_bounds__(256) void k_iagl_link(ModemParams<T> mp, IaglShape 
                         if (a < nr) {
                             const uint32_t pos = (uint32_t)(k * nr + a) * NS + t;
                             if constexpr (PAIR) cn_pair_lds(rng, STREAM_NOISE, pos >> 1, sigma, nz[0][a], nz[COLS - 1][a], s_bm);
-                            else nz[0][a] = iagl_cn_one(rng, STREAM_NOISE, pos, sigma, s_bm);
+                            else nz[0][a] = cn_one_lds(rng, STREAM_NOISE, pos, sigma, s_bm);
                         }
 #pragma unroll
                     for (int j = 0; j < D; ++j)
@@ -295,9 +284,7 @@ __global__ __launch_bounds__(256) void k_iagl_link(ModemParams<T> mp, IaglShape 
                 if (ssym_out) ssym_out[rl * SLOTS + lane] = se;
                 if (sbit_out) sbit_out[rl * SLOTS + lane] = be;
             }
-            se = wave_sum_u32(se);
-            be = wave_sum_u32(be);
-            if (lane == 0) wg_account(totals, se, be, !ok, rl, sym_out, bit_out);
+            link_account(totals, se, be, !ok, rl, lane, sym_out, bit_out);
             wave_lds_sync();
         }
     }
@@ -365,9 +352,7 @@ static int launch_run_ia_general(mcle_ctx* ctx, const mcle_ia_general_cfg* cfg, 
         hipLaunchKernelGGL(k_iagl_record<T>, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, ctx->stream, sh, s_H, s_F, s_U, s_ns,
                            s_sk, s_sinr, s_rec, o.sinr ? o.sinr + off * (kIagUsers * kIaglSlots) : nullptr, m);
         MCLE_LAUNCH_CHECK();
-        const uint64_t resident = (uint64_t)ctx->n_cu * 2;                               // workgroups of four wavefronts
-        const uint64_t chunks = (m + per_wave - 1) / per_wave;
-        const unsigned grid = (unsigned)oversubscribed_grid(ctx, resident, (chunks + 3) / 4, min_units);
+        const unsigned grid = walk_grid(ctx, 2, m, per_wave, min_units);
         uint32_t* se = o.sym ? o.sym + off : nullptr;
         uint32_t* be = o.bit ? o.bit + off : nullptr;
         uint32_t* sse = o.ssym ? o.ssym + off * (kIagUsers * kIaglSlots) : nullptr;
@@ -417,7 +402,6 @@ int mcle_run_ia_general(mcle_ctx* ctx, int dtype, const mcle_ia_general_cfg* cfg
     if (rc) return rc;
     if ((rc = ia_general_check(cfg, true))) return rc;     // the start of MCLE_IA_INIT_GIVEN is drawn here
     MCLE_REQUIRE(n_symbols >= 1, "n_symbols must be positive");
-    MCLE_REQUIRE(count <= 0x7fffffffull, "at most 2^31-1 realizations per call");
     IaglShape sh;
     sh.K = cfg->K, sh.nr = cfg->nr, sh.nt = cfg->nt, sh.D = ia_general_capacity(cfg);
     sh.S0 = 0;
@@ -427,9 +411,8 @@ int mcle_run_ia_general(mcle_ctx* ctx, int dtype, const mcle_ia_general_cfg* cfg
     }
     sh.n_symbols = n_symbols;
     sh.draw_start = cfg->initialize_with == MCLE_IA_INIT_GIVEN;
-    MCLE_REQUIRE((uint64_t)sh.S0 * (uint64_t)n_symbols <= 0x7fffffffull &&
-                     (uint64_t)cfg->K * cfg->nr * (uint64_t)n_symbols <= 0x7fffffffull,
-                 "n_symbols too large: draw positions are 32-bit");
+    // rows: the S0 streams' data, the K nr receive antennas' noise
+    if ((rc = check_link_draws((uint64_t)(sh.S0 > cfg->K * cfg->nr ? sh.S0 : cfg->K * cfg->nr), n_symbols, count))) return rc;
     if (count == 0) return MCLE_OK;
     if ((rc = ctx->bind())) return rc;
     const IaglOut o{d_sym_err, d_bit_err, d_stream_sym_err, d_stream_bit_err, d_ns, d_sinr, d_capacity, d_iterations,

@@ -18,6 +18,7 @@
 #include "totals.hpp"
 #include "qam_pack.hpp"
 #include "wave_draws.hpp"
+#include "link_walk.hpp"
 
 namespace mcle {
 
@@ -194,27 +195,14 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? MCLE_F32_WALK_WAVES : 2) void
     __shared__ float4 s_tab4[sizeof(T) == 4 ? 256 : 1];     // {re, im, |c|^2 / 2, 0}: the lockstep searches of modem.hpp
     extern __shared__ unsigned long long s_grid[];       // [G*G] candidate grid (min-distance demodulation, f32)
     __shared__ double s_bm[sizeof(T) == 8 ? kBmLdsDoubles : 1];   // complex128 Box-Muller tables (bm_f64.hpp)
-    if constexpr (sizeof(T) == 8) bm_tables_to_lds(s_bm, (int)threadIdx.x, (int)blockDim.x);
-    load_table(mp, s_table);
-    load_grid(mp, s_grid);
-    if constexpr (sizeof(T) == 4)
-        for (int m = threadIdx.x; m < mp.M; m += blockDim.x) {
-            const float2 c = mp.g_table[m];
-            s_tab4[m] = make_float4(c.x, c.y, 0.5f * (c.x * c.x + c.y * c.y), 0.f);
-        }
-    const bool lockstep = sizeof(T) == 4 && mp.method == MCLE_DEMOD_MINDIST && (mp.M <= 8 || mp.grid.G > 0);
+    link_prologue(mp, s_table, s_tab4, s_grid, s_bm);
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const T sigma = (T)sqrt(noise_var);
     const uint32_t mask = (uint32_t)(mp.M - 1);
     const int layers = (scheme == MCLE_MIMO_ALAMOUTI || scheme == MCLE_MIMO_MRT) ? 1 : nt;
     const bool c_order = scheme == MCLE_MIMO_SVD || scheme == MCLE_MIMO_GMD;
-    const bool packed = sizeof(T) == 4 && mp.method == MCLE_DEMOD_QAM_SLICER;
-    const uint32_t layer_mask = layers >= 4 ? 0xFFFFFFFFu : ((1u << (8 * layers)) - 1u);
-    QamPack qp{};
-    if constexpr (sizeof(T) == 4) {
-        if (packed) qp = qam_pack(mp);
-    }
+    const LinkDecide<T> w = link_decide_for(mp, s_table, s_tab4, s_grid, layers);
     __shared__ WgTotals totals_all[4];
     WgTotals& totals = totals_all[wv];
     if (lane == 0) wg_zero(totals);
@@ -287,35 +275,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? MCLE_F32_WALK_WAVES : 2) void
                             }
                         }
                     }
-                    if constexpr (sizeof(T) == 4) {
-                        if (packed) {   // the column's decisions in one packed level-domain slice (qam_pack.hpp)
-                            const f4q er = {est[0].x, est[1].x, est[2].x, est[3].x}, ei = {est[0].y, est[1].y, est[2].y, est[3].y};
-                            const uint32_t sent = (uint32_t)tx[0] | ((uint32_t)tx[1] << 8) | ((uint32_t)tx[2] << 16) |
-                                                  ((uint32_t)tx[3] << 24);
-                            qam_count4((qam_levels4(er, ei, qp) ^ labels_to_levels(sent, qp)) & layer_mask, qp, se, be);
-                            return;
-                        }
-                    }
-                    int dec[kFlatMax];
-                    bool done = false;
-                    if constexpr (sizeof(T) == 4) {
-                        if (lockstep) {   // the layers searched in lockstep; unused layers carry est = 0 and are not counted
-                            if (mp.M <= 8) demod_multi_cert(mp, est, dec, [&](int (&d_)[kFlatMax]) { demod_mindist_multi<kFlatMax>(s_tab4, mp.M, est, d_); });
-                            else demod_multi_cert(mp, est, dec, [&](int (&d_)[kFlatMax]) { demod_grid4_multi<kFlatMax>(s_tab4, s_grid, mp.grid, mp.M, est, d_); });
-                            done = true;
-                        }
-                    }
-                    if (!done) {
-#pragma unroll
-                        for (int l = 0; l < kFlatMax; ++l) dec[l] = l < layers ? demod_one(mp, s_table, s_grid, est[l]) : 0;
-                    }
-#pragma unroll
-                    for (int l = 0; l < kFlatMax; ++l)
-                        if (l < layers) {
-                            const unsigned xr = (unsigned)(tx[l] ^ dec[l]);
-                            se += (xr != 0u);
-                            be += __popc(xr);
-                        }
+                    link_decide<T, kFlatMax>(w, est, tx, se, be);
                 };
                 if ((n_symbols & 1) == 0) {
                     for (int t0 = 0; t0 < n_symbols; t0 += kPairCols) {
@@ -326,27 +286,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? MCLE_F32_WALK_WAVES : 2) void
                         if (c_order) {
                             wave_symbol_pairs<kFlatMax>(rng, layers, (uint32_t)n_symbols, (uint32_t)t0, mask, lane, ta, tb);
                         } else if (t < n_symbols) {
-                            // Fortran order: the 2 * layers bytes of columns t, t + 1 are consecutive (<= 8 bytes,
-                            // in one block unless layers == 3)
-                            const uint32_t q = (uint32_t)t * (uint32_t)layers;
-                            const Words4 b0 = rng.block(STREAM_DATA, q >> 4);
-                            Words4 b1 = b0;
-                            if ((q & 15u) + 2u * (uint32_t)layers > 16u) b1 = rng.block(STREAM_DATA, (q >> 4) + 1u);
-#pragma unroll
-                            for (int e = 0; e < 2 * kFlatMax; ++e)
-                                if (e < 2 * layers) {
-                                    const uint32_t pos = (q & 15u) + (uint32_t)e;          // 0 .. 31
-                                    const uint32_t wi = (pos >> 2) & 3u;
-                                    const uint32_t lo = wi == 0 ? b0.w[0] : (wi == 1 ? b0.w[1] : (wi == 2 ? b0.w[2] : b0.w[3]));
-                                    const uint32_t hi = wi == 0 ? b1.w[0] : (wi == 1 ? b1.w[1] : (wi == 2 ? b1.w[2] : b1.w[3]));
-                                    const int v = (int)(((pos < 16u ? lo : hi) >> ((pos & 3u) * 8u)) & mask);
-                                    // e = column * layers + layer
-#pragma unroll
-                                    for (int l = 0; l < kFlatMax; ++l) {
-                                        if (e == l) ta[l] = v;
-                                        if (e == layers + l) tb[l] = v;
-                                    }
-                                }
+                            fortran_symbol_pair<kFlatMax>(rng, layers, (uint32_t)t, mask, ta, tb);
                         }
                         if (t < n_symbols) {
                             cx<T> za[kFlatMax], zb[kFlatMax];
@@ -380,12 +320,36 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? MCLE_F32_WALK_WAVES : 2) void
                     }
                 }
             }
-            se = wave_sum_u32(se);
-            be = wave_sum_u32(be);
-            if (lane == 0) wg_account(totals, se, be, rec[2 * kFlatMax * kFlatMax].y == (T)0, rl, sym_out, bit_out);
+            link_account(totals, se, be, rec[2 * kFlatMax * kFlatMax].y == (T)0, rl, lane, sym_out, bit_out);
         }
     }
     wg_flush_waves<4>(totals_all, counters, (unsigned long long)layers * n_symbols, (unsigned long long)layers * n_symbols * mp.bits);
+}
+
+// The walk keeps its own grid rule (round 2, measured then): at most the resident set, 16 wavefronts per CU in complex64 and 8 in
+// complex128, not oversubscribed.
+template <typename T>
+static int run_mimo_flat(mcle_ctx* ctx, const mcle_mimo_flat_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
+                         mcle_counters* d_counters, uint32_t* d_sym_err, uint32_t* d_bit_err) {
+    const int nt = cfg->nt, nr = cfg->nr;
+    const double filter_nv = cfg->mmse ? cfg->noise_var : 0.0;
+    const int per_wave = 16;
+    const ModemParams<T> mp = pipe_modem<T>(ctx, cfg->demod_method);
+    const size_t lds = (size_t)mp.grid.G * mp.grid.G * sizeof(unsigned long long);
+    const uint64_t kSlice = 1ull << 20;          // realizations per set-up + walk pair: bounds the record buffer
+    const uint64_t cap = (uint64_t)ctx->n_cu * (sizeof(T) == 4 ? 16 : 8);
+    return launch_sliced(
+        ctx, first, count, kSlice, kFlatRec * sizeof(cx<T>), d_sym_err, d_bit_err,
+        [&](void* recs, uint64_t at, uint64_t m) {
+            hipLaunchKernelGGL(k_mimo_flat_setup<T>, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, ctx->stream, cfg->scheme, nt, nr,
+                               filter_nv, seed, at, m, (cx<T>*)recs);
+        },
+        [&](void* recs, uint64_t at, uint64_t m, uint32_t* se, uint32_t* be) {
+            const uint64_t chunks = (m + per_wave - 1) / per_wave;
+            hipLaunchKernelGGL(k_mimo_flat_link<T>, dim3((unsigned)((chunks + 3) / 4 < cap / 4 ? (chunks + 3) / 4 : cap / 4)), dim3(256),
+                               lds, ctx->stream, mp, cfg->scheme, nt, nr, cfg->n_symbols, cfg->noise_var, seed, at, m, per_wave,
+                               (const cx<T>*)recs, d_counters, se, be);
+        });
 }
 
 }  // namespace mcle
@@ -419,42 +383,9 @@ extern "C" int mcle_run_mimo_flat(mcle_ctx* ctx, int dtype, const mcle_mimo_flat
         default:
             MCLE_REQUIRE(nt == nr && nt >= 2, "SVD / GMD filters support square channels with 2 <= N <= 4");
     }
-    MCLE_REQUIRE(count <= 0x7fffffffull, "at most 2^31-1 realizations per call");
+    if ((rc = check_link_draws((uint64_t)(nr > nt ? nr : nt), cfg->n_symbols, count))) return rc;
     if (count == 0) return MCLE_OK;
     if ((rc = ctx->bind())) return rc;
-    const double filter_nv = cfg->mmse ? cfg->noise_var : 0.0;
-    const int per_wave = 16;
-    const ModemParams<float> mp32 = pipe_modem<float>(ctx, cfg->demod_method);
-    const size_t lds = (size_t)mp32.grid.G * mp32.grid.G * sizeof(unsigned long long);
-    const uint64_t kSlice = 1ull << 20;          // realizations per set-up + walk pair: bounds the record buffer
-    const uint64_t slice = count < kSlice ? count : kSlice;
-    void* recs = nullptr;
-    if ((rc = ctx->scratch((size_t)slice * kFlatRec * (dtype == MCLE_F32 ? sizeof(float2) : sizeof(double2)), &recs)))
-        return rc;
-    for (uint64_t off = 0; off < count; off += slice) {
-        const uint64_t m = count - off < slice ? count - off : slice;
-        const uint64_t chunks = (m + per_wave - 1) / per_wave;
-        const unsigned sgrid = (unsigned)((m + 63) / 64);
-        uint32_t* se = d_sym_err ? d_sym_err + off : nullptr;
-        uint32_t* be = d_bit_err ? d_bit_err + off : nullptr;
-        if (dtype == MCLE_F32) {
-            const uint64_t cap = (uint64_t)ctx->n_cu * 16;
-            hipLaunchKernelGGL(k_mimo_flat_setup<float>, dim3(sgrid), dim3(64), 0, ctx->stream, cfg->scheme, nt, nr, filter_nv,
-                               seed, first + off, m, (float2*)recs);
-            MCLE_LAUNCH_CHECK();
-            hipLaunchKernelGGL(k_mimo_flat_link<float>, dim3((unsigned)((chunks + 3) / 4 < cap / 4 ? (chunks + 3) / 4 : cap / 4)), dim3(256), lds,
-                               ctx->stream, mp32, cfg->scheme, nt, nr, cfg->n_symbols, cfg->noise_var, seed, first + off, m,
-                               per_wave, (const float2*)recs, d_counters, se, be);
-        } else {
-            const uint64_t cap = (uint64_t)ctx->n_cu * 8;
-            hipLaunchKernelGGL(k_mimo_flat_setup<double>, dim3(sgrid), dim3(64), 0, ctx->stream, cfg->scheme, nt, nr, filter_nv,
-                               seed, first + off, m, (double2*)recs);
-            MCLE_LAUNCH_CHECK();
-            hipLaunchKernelGGL(k_mimo_flat_link<double>, dim3((unsigned)((chunks + 3) / 4 < cap / 4 ? (chunks + 3) / 4 : cap / 4)), dim3(256), lds,
-                               ctx->stream, pipe_modem<double>(ctx, cfg->demod_method), cfg->scheme, nt, nr, cfg->n_symbols,
-                               cfg->noise_var, seed, first + off, m, per_wave, (const double2*)recs, d_counters, se, be);
-        }
-        MCLE_LAUNCH_CHECK();
-    }
-    return MCLE_OK;
+    return dtype == MCLE_F32 ? run_mimo_flat<float>(ctx, cfg, seed, first, count, d_counters, d_sym_err, d_bit_err)
+                             : run_mimo_flat<double>(ctx, cfg, seed, first, count, d_counters, d_sym_err, d_bit_err);
 }

@@ -22,6 +22,8 @@
 #include "philox.hpp"
 #include "pipe_common.hpp"
 #include "totals.hpp"
+#include "wave_draws.hpp"
+#include "link_walk.hpp"
 
 namespace mcle {
 
@@ -163,13 +165,6 @@ constexpr bool large_link_matches_map() {
 }
 static_assert(large_link_matches_map(), "k_mimo_large_link and mimo_large_map.hpp disagree");
 
-// symbol n of the data stream out of its block: byte n & 15 of the four words (symbol_at).  By 64-bit shifts, not by selects of
-// b.w[i]: the backend turns those into a lane-indexed read of the block parked in scratch (philox.hpp: cn_sample)
-__device__ __forceinline__ int large_symbol(const Words4& b, uint32_t n, uint32_t mask) {
-    const uint64_t lo = (uint64_t)b.w[0] | ((uint64_t)b.w[1] << 32), hi = (uint64_t)b.w[2] | ((uint64_t)b.w[3] << 32);
-    return (int)((uint32_t)(((n & 8u) ? hi : lo) >> ((n & 7u) * 8u)) & mask);
-}
-
 template <typename T>
 __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void k_mimo_large_link(
     ModemParams<T> mp, int nt, int nr, int n_symbols, double noise_var, uint64_t seed, uint64_t first, uint64_t count,
@@ -180,9 +175,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void k_mimo_large_link
     __shared__ cx<T> s_table[256];
     extern __shared__ unsigned long long s_grid[];       // [G*G] candidate grid (min-distance demodulation)
     __shared__ double s_bm[sizeof(T) == 8 ? kBmLdsDoubles : 1];   // complex128 Box-Muller tables (bm_f64.hpp)
-    if constexpr (sizeof(T) == 8) bm_tables_to_lds(s_bm, (int)threadIdx.x, (int)blockDim.x);
-    load_table(mp, s_table);
-    load_grid(mp, s_grid);
+    link_prologue(mp, s_table, nullptr, s_grid, s_bm);     // (no lockstep table: demod_one per stream)
     const int lane = threadIdx.x & 63, g = lane >> 4, n = lane & 15;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const T sigma = (T)sqrt(noise_var);
@@ -218,12 +211,12 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void k_mimo_large_link
                         if (a < nt && t < n_symbols) {
                             const uint32_t n0 = (uint32_t)t * (uint32_t)nt + (uint32_t)a, n1 = n0 + (uint32_t)nt;
                             const Words4 b0 = rng.block(STREAM_DATA, n0 >> 4);
-                            tx0[p] = large_symbol(b0, n0, mask);
+                            tx0[p] = block_symbol(b0, n0, mask);
                             x0 = s_table[tx0[p]];
                             if (t + 1 < n_symbols) {
                                 Words4 b1 = b0;
                                 if ((n1 >> 4) != (n0 >> 4)) b1 = rng.block(STREAM_DATA, n1 >> 4);
-                                tx1[p] = large_symbol(b1, n1, mask);
+                                tx1[p] = block_symbol(b1, n1, mask);
                                 x1 = s_table[tx1[p]];
                             }
                         }
@@ -267,9 +260,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void k_mimo_large_link
                         }
                     }
             }
-            se = wave_sum_u32(se);
-            be = wave_sum_u32(be);
-            if (lane == 0) wg_account(totals, se, be, flags[rl] == 0u, rl, sym_out, bit_out);
+            link_account(totals, se, be, flags[rl] == 0u, rl, lane, sym_out, bit_out);
         }
     }
     wg_flush_waves<4>(totals_all, counters, (unsigned long long)nt * n_symbols, (unsigned long long)nt * n_symbols * mp.bits);
@@ -286,33 +277,31 @@ static int run_mimo_large(mcle_ctx* ctx, const mcle_mimo_large_cfg* cfg, uint64_
     // record: 64 values of the link's arithmetic per K-step, then one flag word -- at most 6 KiB per realization (8 x 16,
     // complex128), so the slice is sized by bytes: at most 128 MiB of records
     const size_t rec_bytes = (size_t)mimo_large_record_len(nt, nr) * sizeof(T);
-    uint64_t slice = (((uint64_t)128 << 20) / rec_bytes) & ~(uint64_t)3;
-    if (count < slice) slice = count;
-    void* recs = nullptr;
-    int rc;
-    if ((rc = ctx->scratch((size_t)slice * (rec_bytes + sizeof(uint32_t)), &recs))) return rc;
-    uint32_t* flags = reinterpret_cast<uint32_t*>(static_cast<char*>(recs) + (size_t)slice * rec_bytes);
-    const uint64_t wgs_per_cu = sizeof(T) == 4 ? 3 : 2;
-    for (uint64_t off = 0; off < count; off += slice) {
-        const uint64_t m = count - off < slice ? count - off : slice;
-        const unsigned sgrid = (unsigned)((m + 3) / 4);
+    const uint64_t k_slice = (((uint64_t)128 << 20) / rec_bytes) & ~(uint64_t)3;
+    const uint64_t slice = count < k_slice ? count : k_slice;
+    int rc = launch_sliced(
+        ctx, first, count, k_slice, rec_bytes, d_sym_err, d_bit_err,
+        [&](void* recs, uint64_t at, uint64_t m) {
+            uint32_t* flags = reinterpret_cast<uint32_t*>(static_cast<char*>(recs) + (size_t)slice * rec_bytes);
+            const unsigned sgrid = (unsigned)((m + 3) / 4);
 #define MCLE_LS(NT_)                                                                                                             \
     case NT_:                                                                                                                    \
-        hipLaunchKernelGGL(k_mimo_large_setup<NT_>, dim3(sgrid), dim3(64), 0, ctx->stream, nr, filter_nv, seed, first + off, m,  \
+        hipLaunchKernelGGL(k_mimo_large_setup<NT_>, dim3(sgrid), dim3(64), 0, ctx->stream, nr, filter_nv, seed, at, m,           \
                            (int)(sizeof(T) == 8), recs, flags);                                                                  \
         break;
-        switch (nt) {
-            MCLE_LS(1) MCLE_LS(2) MCLE_LS(3) MCLE_LS(4) MCLE_LS(5) MCLE_LS(6) MCLE_LS(7) MCLE_LS(8)
-        }
+            switch (nt) {
+                MCLE_LS(1) MCLE_LS(2) MCLE_LS(3) MCLE_LS(4) MCLE_LS(5) MCLE_LS(6) MCLE_LS(7) MCLE_LS(8)
+            }
 #undef MCLE_LS
-        MCLE_LAUNCH_CHECK();
-        const uint64_t chunks = (m + per_wave - 1) / per_wave;
-        const uint64_t grid = oversubscribed_grid(ctx, (uint64_t)ctx->n_cu * wgs_per_cu, (chunks + 3) / 4);
-        hipLaunchKernelGGL(k_mimo_large_link<T>, dim3((unsigned)grid), dim3(256), lds, ctx->stream, mp, nt, nr, cfg->n_symbols,
-                           cfg->noise_var, seed, first + off, m, per_wave, (const T*)recs, (const uint32_t*)flags, d_counters,
-                           d_sym_err ? d_sym_err + off : nullptr, d_bit_err ? d_bit_err + off : nullptr);
-        MCLE_LAUNCH_CHECK();
-    }
+        },
+        [&](void* recs, uint64_t at, uint64_t m, uint32_t* se, uint32_t* be) {
+            const uint32_t* flags = reinterpret_cast<const uint32_t*>(static_cast<char*>(recs) + (size_t)slice * rec_bytes);
+            hipLaunchKernelGGL(k_mimo_large_link<T>, dim3(walk_grid(ctx, sizeof(T) == 4 ? 3 : 2, m, per_wave)), dim3(256), lds, ctx->stream,
+                               mp, nt, nr, cfg->n_symbols, cfg->noise_var, seed, at, m, per_wave, (const T*)recs, flags, d_counters, se,
+                               be);
+        },
+        sizeof(uint32_t));
+    if (rc) return rc;
     ctx->set_kernel("mimo_large_link %s %dx%d s%d", sizeof(T) == 8 ? "f64" : "f32", nr, nt, steps);
     return MCLE_OK;
 }
@@ -330,11 +319,10 @@ extern "C" int mcle_run_mimo_large(mcle_ctx* ctx, int dtype, const mcle_mimo_lar
     MCLE_REQUIRE(nt >= 1 && nt <= kLargeMaxNt && nr >= nt && nr <= kLargeMaxNr,
                  "antenna counts must satisfy 1 <= nt <= %d, nt <= nr <= %d (got nt %d, nr %d)", kLargeMaxNt, kLargeMaxNr, nt, nr);
     MCLE_REQUIRE(cfg->n_symbols >= 1, "n_symbols must be positive");
-    MCLE_REQUIRE((uint64_t)nr * (uint64_t)cfg->n_symbols <= 0x7fffffffull, "n_symbols too large: draw positions are 32-bit");
     MCLE_REQUIRE(cfg->noise_var >= 0.0 && cfg->noise_var <= 1.79e308, "Noise variance must be a non-negative value.");
     MCLE_REQUIRE(cfg->mmse == 0 || cfg->mmse == 1, "mmse must be 0 or 1 (got %d)", cfg->mmse);
     MCLE_REQUIRE(cfg->reserved == 0, "reserved must be 0");
-    MCLE_REQUIRE(count <= 0x7fffffffull, "at most 2^31-1 realizations per call");
+    if ((rc = check_link_draws((uint64_t)nr, cfg->n_symbols, count))) return rc;
     if (count == 0) return MCLE_OK;
     if ((rc = ctx->bind())) return rc;
     return dtype == MCLE_F32 ? run_mimo_large<float>(ctx, cfg, seed, first, count, d_counters, d_sym_err, d_bit_err)

@@ -103,10 +103,10 @@ __global__ __launch_bounds__(kPipeBlock, WAVES) void k_run_mimo_ofdm_mfma(MimoPa
     const bool slicer = mp.method == MCLE_DEMOD_QAM_SLICER;   // s_idx then holds LEVEL bytes instead of labels
     const QamPack qp = qam_pack(mp);
 
+    load_tab4(mp, s_tab4);
     for (int m = tid; m < mp.M; m += kPipeBlock) {
         const float2 c = mp.g_table[m];
         s_txtab[m] = make_float2(c.x * tx_scale, c.y * tx_scale);
-        s_tab4[m] = make_float4(c.x, c.y, 0.5f * (c.x * c.x + c.y * c.y), 0.f);
     }
     load_grid(mp, s_grid);
     __shared__ WgTotals totals;

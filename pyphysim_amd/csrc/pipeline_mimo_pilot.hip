@@ -32,6 +32,7 @@
 #include "qam_pack.hpp"
 #include "totals.hpp"
 #include "wave_draws.hpp"
+#include "link_walk.hpp"
 
 namespace mcle {
 
@@ -249,62 +250,16 @@ __global__ __launch_bounds__(64) void k_mimo_pilot_setup(PilotSetup p, const dou
     rec[2 * kPilotSet] = mk<T>(ok ? (T)1 : (T)0, (T)0);
 }
 
-// what the decisions of a column need, fixed for the launch
-template <typename T> struct PilotWalk {
-    const ModemParams<T>& mp;
-    const cx<T>* s_table;
-    const float4* s_tab4;
-    const unsigned long long* s_grid;
-    QamPack qp;
-    uint32_t layer_mask;
-    bool lockstep, packed;
-    int nt, nr;
-};
-
-// the decisions of one column and their errors: the Blast branch of k_mimo_flat_link's column
-template <typename T>
-__device__ __forceinline__ void pilot_decide(const PilotWalk<T>& w, const cx<T> (&est)[kPilotMax], const int (&tx)[kPilotMax],
-                                             unsigned& se, unsigned& be) {
-    if constexpr (sizeof(T) == 4) {
-        if (w.packed) {   // the column's decisions in one packed level-domain slice (qam_pack.hpp)
-            const f4q er = {est[0].x, est[1].x, est[2].x, est[3].x}, ei = {est[0].y, est[1].y, est[2].y, est[3].y};
-            const uint32_t sent = (uint32_t)tx[0] | ((uint32_t)tx[1] << 8) | ((uint32_t)tx[2] << 16) | ((uint32_t)tx[3] << 24);
-            qam_count4((qam_levels4(er, ei, w.qp) ^ labels_to_levels(sent, w.qp)) & w.layer_mask, w.qp, se, be);
-            return;
-        }
-    }
-    int dec[kPilotMax];
-    bool done = false;
-    if constexpr (sizeof(T) == 4) {
-        if (w.lockstep) {   // the layers searched in lockstep; unused layers carry est = 0 and are not counted
-            if (w.mp.M <= 8) demod_multi_cert(w.mp, est, dec, [&](int (&d_)[kPilotMax]) { demod_mindist_multi<kPilotMax>(w.s_tab4, w.mp.M, est, d_); });
-            else demod_multi_cert(w.mp, est, dec, [&](int (&d_)[kPilotMax]) { demod_grid4_multi<kPilotMax>(w.s_tab4, w.s_grid, w.mp.grid, w.mp.M, est, d_); });
-            done = true;
-        }
-    }
-    if (!done) {
-#pragma unroll
-        for (int l = 0; l < kPilotMax; ++l) dec[l] = l < w.nt ? demod_one(w.mp, w.s_table, w.s_grid, est[l]) : 0;
-    }
-#pragma unroll
-    for (int l = 0; l < kPilotMax; ++l)
-        if (l < w.nt) {
-            const unsigned xr = (unsigned)(tx[l] ^ dec[l]);
-            se += (xr != 0u);
-            be += __popc(xr);
-        }
-}
-
 // COLS symbol columns of one lane through both filters: est = A d + G n per filter, in the association of k_mimo_flat_link; an
 // entry of the record (the wavefront's LDS copy) is read once and serves every column
 template <typename T, int COLS>
-__device__ __forceinline__ void pilot_columns(const PilotWalk<T>& w, const cx<T>* s_rec, const int (&tx)[COLS][kPilotMax],
+__device__ __forceinline__ void pilot_columns(const LinkDecide<T>& w, int nr, const cx<T>* s_rec, const int (&tx)[COLS][kPilotMax],
                                               const cx<T> (&nz)[COLS][kPilotMax], unsigned (&se)[2], unsigned (&be)[2]) {
     cx<T> d[COLS][kPilotMax];
 #pragma unroll
     for (int c = 0; c < COLS; ++c)
 #pragma unroll
-        for (int l = 0; l < kPilotMax; ++l) d[c][l] = l < w.nt ? w.s_table[tx[c][l]] : mk<T>(0, 0);
+        for (int l = 0; l < kPilotMax; ++l) d[c][l] = l < w.layers ? w.s_table[tx[c][l]] : mk<T>(0, 0);
 #pragma unroll
     for (int set = 0; set < 2; ++set) {
         const cx<T>* A = s_rec + set * kPilotSet;
@@ -314,15 +269,15 @@ __device__ __forceinline__ void pilot_columns(const PilotWalk<T>& w, const cx<T>
         for (int l = 0; l < kPilotMax; ++l) {
 #pragma unroll
             for (int c = 0; c < COLS; ++c) est[c][l] = mk<T>(0, 0);
-            if (l < w.nt) {
+            if (l < w.layers) {
 #pragma unroll
                 for (int k = 0; k < kPilotMax; ++k) {
-                    if (k < w.nt) {
+                    if (k < w.layers) {
                         const cx<T> a = A[l * kPilotMax + k];
 #pragma unroll
                         for (int c = 0; c < COLS; ++c) est[c][l] = cfma4(a, d[c][k], est[c][l]);
                     }
-                    if (k < w.nr) {
+                    if (k < nr) {
                         const cx<T> g = G[l * kPilotMax + k];
 #pragma unroll
                         for (int c = 0; c < COLS; ++c) est[c][l] = cfma4(g, nz[c][k], est[c][l]);
@@ -331,7 +286,7 @@ __device__ __forceinline__ void pilot_columns(const PilotWalk<T>& w, const cx<T>
             }
         }
 #pragma unroll
-        for (int c = 0; c < COLS; ++c) pilot_decide<T>(w, est[c], tx[c], se[set], be[set]);
+        for (int c = 0; c < COLS; ++c) link_decide<T, kPilotMax>(w, est[c], tx[c], se[set], be[set]);
     }
 }
 
@@ -350,24 +305,12 @@ __global__ __launch_bounds__(256, pilot_walk_waves<T>()) void k_mimo_pilot_link(
     __shared__ double s_bm[sizeof(T) == 8 ? kBmLdsDoubles : 1];   // complex128 Box-Muller tables (bm_f64.hpp)
     __shared__ cx<T> s_rec_all[4][kPilotRec + 1];           // each wavefront's current record
     __shared__ WgTotals totals_all[2][4];                   // [estimated | perfect CSI][wavefront]
-    if constexpr (sizeof(T) == 8) bm_tables_to_lds(s_bm, (int)threadIdx.x, (int)blockDim.x);
-    load_table(mp, s_table);
-    load_grid(mp, s_grid);
-    if constexpr (sizeof(T) == 4)
-        for (int m = threadIdx.x; m < mp.M; m += blockDim.x) {
-            const float2 c = mp.g_table[m];
-            s_tab4[m] = make_float4(c.x, c.y, 0.5f * (c.x * c.x + c.y * c.y), 0.f);
-        }
+    link_prologue(mp, s_table, s_tab4, s_grid, s_bm);
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const T sigma = (T)sqrt(noise_var);
     const uint32_t mask = (uint32_t)(mp.M - 1);
-    PilotWalk<T> w{mp, s_table, s_tab4, s_grid, QamPack{}, nt >= 4 ? 0xFFFFFFFFu : ((1u << (8 * nt)) - 1u),
-                   sizeof(T) == 4 && mp.method == MCLE_DEMOD_MINDIST && (mp.M <= 8 || mp.grid.G > 0),
-                   sizeof(T) == 4 && mp.method == MCLE_DEMOD_QAM_SLICER, nt, nr};
-    if constexpr (sizeof(T) == 4) {
-        if (w.packed) w.qp = qam_pack(mp);
-    }
+    const LinkDecide<T> w = link_decide_for(mp, s_table, s_tab4, s_grid, nt);
     cx<T>* s_rec = s_rec_all[wv];
     if (lane == 0) {
         wg_zero(totals_all[0][wv]);
@@ -393,27 +336,7 @@ __global__ __launch_bounds__(256, pilot_walk_waves<T>()) void k_mimo_pilot_link(
                         int tx[2][kPilotMax];
 #pragma unroll
                         for (int l = 0; l < kPilotMax; ++l) tx[0][l] = tx[1][l] = 0;
-                        // Fortran order: the 2 nt bytes of columns t, t + 1 are consecutive (<= 8 bytes, in one block unless
-                        // nt == 3)
-                        const uint32_t q = (uint32_t)t * (uint32_t)nt;
-                        const Words4 b0 = rng.block(STREAM_DATA, q >> 4);
-                        Words4 b1 = b0;
-                        if ((q & 15u) + 2u * (uint32_t)nt > 16u) b1 = rng.block(STREAM_DATA, (q >> 4) + 1u);
-#pragma unroll
-                        for (int e = 0; e < 2 * kPilotMax; ++e)
-                            if (e < 2 * nt) {
-                                const uint32_t pos = (q & 15u) + (uint32_t)e;          // 0 .. 31
-                                const uint32_t wi = (pos >> 2) & 3u;
-                                const uint32_t lo = wi == 0 ? b0.w[0] : (wi == 1 ? b0.w[1] : (wi == 2 ? b0.w[2] : b0.w[3]));
-                                const uint32_t hi = wi == 0 ? b1.w[0] : (wi == 1 ? b1.w[1] : (wi == 2 ? b1.w[2] : b1.w[3]));
-                                const int v = (int)(((pos < 16u ? lo : hi) >> ((pos & 3u) * 8u)) & mask);
-                                // e = column * nt + layer
-#pragma unroll
-                                for (int l = 0; l < kPilotMax; ++l) {
-                                    if (e == l) tx[0][l] = v;
-                                    if (e == nt + l) tx[1][l] = v;
-                                }
-                            }
+                        fortran_symbol_pair<kPilotMax>(rng, nt, (uint32_t)t, mask, tx[0], tx[1]);
                         cx<T> nz[2][kPilotMax];
 #pragma unroll
                         for (int r = 0; r < kPilotMax; ++r) {
@@ -422,7 +345,7 @@ __global__ __launch_bounds__(256, pilot_walk_waves<T>()) void k_mimo_pilot_link(
                                 cn_pair_lds(rng, STREAM_NOISE, ((uint32_t)r * (uint32_t)n_symbols + (uint32_t)t) >> 1, sigma,
                                             nz[0][r], nz[1][r], s_bm);
                         }
-                        pilot_columns<T, 2>(w, s_rec, tx, nz, se, be);
+                        pilot_columns<T, 2>(w, nr, s_rec, tx, nz, se, be);
                     }
                 }
             } else {
@@ -435,16 +358,14 @@ __global__ __launch_bounds__(256, pilot_walk_waves<T>()) void k_mimo_pilot_link(
 #pragma unroll
                     for (int r = 0; r < kPilotMax; ++r)
                         nz[0][r] = r < nr ? cn_sample<T>(rng, STREAM_NOISE, (uint64_t)r * n_symbols + t, sigma) : mk<T>(0, 0);
-                    pilot_columns<T, 1>(w, s_rec, tx, nz, se, be);
+                    pilot_columns<T, 1>(w, nr, s_rec, tx, nz, se, be);
                 }
             }
             const bool skipped = s_rec[2 * kPilotSet].x == (T)0;
 #pragma unroll
             for (int set = 0; set < 2; ++set) {
-                const unsigned s_sum = wave_sum_u32(se[set]), b_sum = wave_sum_u32(be[set]);
-                if (lane == 0)
-                    wg_account(totals_all[set][wv], s_sum, b_sum, skipped, rl, set == 0 ? sym_est : sym_perf,
-                               set == 0 ? bit_est : bit_perf);
+                link_account(totals_all[set][wv], se[set], be[set], skipped, rl, lane, set == 0 ? sym_est : sym_perf,
+                             set == 0 ? bit_est : bit_perf);
             }
             wave_lds_sync();                    // the record's readers, before the next one overwrites it
         }
@@ -516,37 +437,30 @@ static int run_mimo_pilot_link(mcle_ctx* ctx, const mcle_mimo_pilot_cfg* cfg, co
     const size_t lds = (size_t)mp.grid.G * mp.grid.G * sizeof(unsigned long long);
     const int per_wave = 16;
     // records of a slice of realizations, then their walk: at most 512 MiB of records per pair of launches, less on a crowded
-    // device (scratch_upto)
+    // device (down to 64 realizations: launch_sliced's floor)
     const size_t one = (size_t)kPilotRec * sizeof(cx<T>);
-    uint64_t slice = ((size_t)512 << 20) / one;
-    if (slice > count) slice = count;
-    void* recs = nullptr;
-    size_t got = 0;
-    int rc;
-    if ((rc = ctx->scratch_upto((size_t)slice * one, (size_t)(slice < 64 ? slice : 64) * one, &recs, &got))) return rc;
-    if (got / one < slice) slice = got / one;
     // A unit is four chunks = 64 realizations of 2 nt (nt + nr) n_symbols complex multiply-adds each; the workgroup's one flush
     // phase is twelve atomics (pipe_common.hpp: flush_min_units, the estimate of pipeline_ia_general.hip)
     const uint64_t min_units = flush_min_units(2, 1u << 14, 2ull * nt * (nt + nr) * (uint64_t)cfg->n_symbols);
-    const uint64_t resident = (uint64_t)ctx->n_cu * pilot_walk_waves<T>();               // workgroups of four wavefronts
-    for (uint64_t off = 0; off < count; off += slice) {
-        const uint64_t m = count - off < slice ? count - off : slice;
-        double* e_out = d_err ? d_err + off : nullptr;
-        double* p_out = d_pow ? d_pow + off : nullptr;
+    const int rc = launch_sliced(
+        ctx, first, count, ((size_t)512 << 20) / one, one, d_sym_err, d_bit_err,
+        [&](void* recs, uint64_t at, uint64_t m) {
+            const uint64_t off = at - first;
+            double* e_out = d_err ? d_err + off : nullptr;
+            double* p_out = d_pow ? d_pow + off : nullptr;
 #define MCLE_PS(NT_, NR_) \
-    if (nt == NT_ && nr == NR_) launch_pilot_setup<T, NT_, NR_>(ctx, p, d_pilots, d_L, d_B, seed, first + off, m, recs, e_out, p_out);
-        MCLE_PS(1, 1) MCLE_PS(1, 2) MCLE_PS(1, 3) MCLE_PS(1, 4) MCLE_PS(2, 2) MCLE_PS(2, 3) MCLE_PS(2, 4) MCLE_PS(3, 3)
-        MCLE_PS(3, 4) MCLE_PS(4, 4)
+    if (nt == NT_ && nr == NR_) launch_pilot_setup<T, NT_, NR_>(ctx, p, d_pilots, d_L, d_B, seed, at, m, recs, e_out, p_out);
+            MCLE_PS(1, 1) MCLE_PS(1, 2) MCLE_PS(1, 3) MCLE_PS(1, 4) MCLE_PS(2, 2) MCLE_PS(2, 3) MCLE_PS(2, 4) MCLE_PS(3, 3)
+            MCLE_PS(3, 4) MCLE_PS(4, 4)
 #undef MCLE_PS
-        MCLE_LAUNCH_CHECK();
-        const uint64_t chunks = (m + per_wave - 1) / per_wave;
-        const unsigned grid = (unsigned)oversubscribed_grid(ctx, resident, (chunks + 3) / 4, min_units);
-        hipLaunchKernelGGL(k_mimo_pilot_link<T>, dim3(grid), dim3(256), lds, ctx->stream, mp, nt, nr, cfg->n_symbols,
-                           cfg->noise_var, seed, first + off, m, per_wave, (const cx<T>*)recs, d_counters,
-                           d_sym_err ? d_sym_err + off : nullptr, d_bit_err ? d_bit_err + off : nullptr,
-                           d_sym_err ? d_sym_err + count + off : nullptr, d_bit_err ? d_bit_err + count + off : nullptr);
-        MCLE_LAUNCH_CHECK();
-    }
+        },
+        [&](void* recs, uint64_t at, uint64_t m, uint32_t* se, uint32_t* be) {   // the perfect-CSI block follows the estimated one
+            hipLaunchKernelGGL(k_mimo_pilot_link<T>, dim3(walk_grid(ctx, pilot_walk_waves<T>(), m, per_wave, min_units)), dim3(256), lds,
+                               ctx->stream, mp, nt, nr, cfg->n_symbols, cfg->noise_var, seed, at, m, per_wave, (const cx<T>*)recs,
+                               d_counters, se, be, se ? se + count : nullptr, be ? be + count : nullptr);
+        },
+        0, 64);
+    if (rc) return rc;
     ctx->set_kernel("mimo_pilot_link %s %s", sizeof(T) == 8 ? "f64" : "f32", cfg->estimator ? "mmse" : "ls");
     return MCLE_OK;
 }
@@ -576,8 +490,7 @@ extern "C" int mcle_run_mimo_pilot_link(mcle_ctx* ctx, int dtype, const mcle_mim
     MCLE_REQUIRE(cfg->random_pilots || d_pilots != nullptr, "null d_pilots with random_pilots = 0");
     MCLE_REQUIRE(cfg->estimator == 0 || nt == 1, "the MMSE estimator needs nt = 1 (got %d)", nt);
     MCLE_REQUIRE(cfg->estimator == 0 || d_mmse_matrix != nullptr, "the MMSE estimator needs d_mmse_matrix (from a covariance)");
-    MCLE_REQUIRE((uint64_t)nr * (uint64_t)cfg->n_symbols <= 0x7fffffffull, "n_symbols too large: draw positions are 32-bit");
-    MCLE_REQUIRE(count <= 0x7fffffffull, "at most 2^31-1 realizations per call");
+    if ((rc = check_link_draws((uint64_t)nr, cfg->n_symbols, count))) return rc;
     if (count == 0) return MCLE_OK;
     MCLE_REQUIRE(d_counters != nullptr, "null d_counters");
     if ((rc = ctx->bind())) return rc;

@@ -73,13 +73,8 @@ __global__ __launch_bounds__(kPipeBlock, (mimo_tdl_waves<T, N, NA>())) void k_ru
     if constexpr (kTwLds)
         for (int k = tid0; k < N; k += kPipeBlock) s_twbuf[k] = g_tw[k];
     if constexpr (kTwLds) load_grid(mp, s_grid);
-    for (int m = tid0; m < mp.M; m += kPipeBlock) {
-        const cx<T> c = mp.g_table[m];
-        if constexpr (sizeof(T) == 4)
-            s_tab4[m] = make_float4((float)c.x, (float)c.y, (float)(0.5 * (c.x * c.x + c.y * c.y)), 0.f);
-        else
-            s_table[m] = c;
-    }
+    if constexpr (sizeof(T) == 4) load_tab4(mp, s_tab4);
+    else load_table(mp, s_table);
     auto table_at = [&](int m) -> cx<T> {
         if constexpr (sizeof(T) == 4) {
             const float4 c = s_tab4[m];

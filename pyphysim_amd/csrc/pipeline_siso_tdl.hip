@@ -362,9 +362,9 @@ __global__ __launch_bounds__(kPipeBlock, WAVES) void k_run_ofdm_tdl_mfma(
     const uint32_t mask4 = mask * 0x01010101u;
     const double xc = 0.5 * (double)(W - 1);                           // centre of the symbol in local sample units
 
+    load_tab4(mp, s_tab4);
     for (int m = tid; m < mp.M; m += kPipeBlock) {
         const float2 c = mp.g_table[m];
-        s_tab4[m] = make_float4(c.x, c.y, 0.5f * (c.x * c.x + c.y * c.y), 0.f);
         s_txtab[m] = make_float2(c.x * tx_scale, c.y * tx_scale);
     }
     load_grid(mp, s_grid);

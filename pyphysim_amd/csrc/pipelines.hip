@@ -127,11 +127,7 @@ __global__ __launch_bounds__(kPipeBlock, (sizeof(T) == 8 && LR == 8) ? 2 : 1) vo
     if constexpr (sizeof(T) == 8) bm_tables_to_lds(s_bm, (int)threadIdx.x, kPipeBlock);
     load_table(mp, s_table);
     load_grid(mp, s_grid);
-    if constexpr (MODE == 2)
-        for (int m = threadIdx.x; m < mp.M; m += kPipeBlock) {
-            const float2 c = mp.g_table[m];
-            s_tab4[m] = make_float4(c.x, c.y, 0.5f * (c.x * c.x + c.y * c.y), 0.f);
-        }
+    if constexpr (MODE == 2) load_tab4(mp, s_tab4);
     const int chunks = (fp.n_symbols + kChunk - 1) / kChunk;
     const uint64_t items = count * (uint64_t)chunks;
     const T sigma = (T)fp.noise_sigma;
@@ -337,11 +333,7 @@ __global__ __launch_bounds__(kPipeBlock) void k_run_flat_mfma(FlatParams fp, Mod
     __shared__ unsigned s_red[2 * (kPipeBlock / 64)];
     load_table(mp, s_table);
     load_grid(mp, s_grid);
-    if constexpr (MODE == 2)
-        for (int m = threadIdx.x; m < mp.M; m += kPipeBlock) {
-            const float2 c = mp.g_table[m];
-            s_tab4[m] = make_float4(c.x, c.y, 0.5f * (c.x * c.x + c.y * c.y), 0.f);
-        }
+    if constexpr (MODE == 2) load_tab4(mp, s_tab4);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, b = lane >> 4;
     QamPack qp{};
     if constexpr (MODE == 1) qp = qam_pack(mp);
@@ -500,10 +492,7 @@ __global__ __launch_bounds__(kPipeBlock, sizeof(T) == 4 ? 3 : 1) void k_run_mimo
     for (int k = tid; k < N; k += kPipeBlock) s_tw[k] = g_tw[k];
     load_table(mp, s_table);
     load_grid(mp, s_grid);
-    for (int m = tid; m < mp.M; m += kPipeBlock) {
-        const cx<T> c = mp.g_table[m];
-        s_tab4[m] = make_float4((float)c.x, (float)c.y, (float)(0.5 * (c.x * c.x + c.y * c.y)), 0.f);
-    }
+    load_tab4(mp, s_tab4);
     const int U = pp.num_used, cp = pp.cp;
     const int per_sym = U * NA;                       // data symbols per OFDM symbol (all antennas)
     const uint64_t row = (uint64_t)pp.n_ofdm_sym * (N + cp);
