@@ -1001,7 +1001,7 @@ int mcle_run_pilot_mse(mcle_ctx* ctx, int dtype, const mcle_pilot_mse_cfg* cfg, 
  * so with L = I and alpha = 1 block 1 is mcle_run_mimo_flat(MCLE_MIMO_BLAST) on the same (seed, realization).
  * mcle_ctx_last_kernel: "mimo_pilot_link f64|f32 ls|mmse". */
 typedef struct mcle_mimo_pilot_cfg {
-    int32_t nt, nr;            /* 1 <= nt <= nr <= 4 */
+    int32_t nt, nr;            /* 1 <= nt <= nr <= 4 (mcle_run_mimo_large_pilot: 1 <= nt <= 8, nt <= nr <= 16) */
     int32_t n_pilots;          /* nt .. 256 */
     int32_t n_symbols;         /* NSymbs per layer, >= 1 */
     int32_t demod_method;
@@ -1013,6 +1013,29 @@ typedef struct mcle_mimo_pilot_cfg {
 int mcle_run_mimo_pilot_link(mcle_ctx* ctx, int dtype, const mcle_mimo_pilot_cfg* cfg, uint64_t seed, uint64_t first,
                              uint64_t count, const double* d_pilots, const double* d_chan_factor, const double* d_mmse_matrix,
                              mcle_counters* d_counters, uint32_t* d_sym_err, uint32_t* d_bit_err, double* d_err, double* d_pow);
+
+/* The same experiment on the large-array link of mcle_run_mimo_large (csrc/pipeline_mimo_large_pilot.hip): how many pilots a
+ * large receive array needs before the estimate stops costing symbol errors.  Model, estimators, outputs, skip rules (a pilot
+ * Gram pivot at or below 1e-12 of the trace, or either filter failing its > 1e-300 pivot test: skipped in BOTH blocks, counted in
+ * n_skipped, 0xFFFFFFFF in the per-realization arrays), the meaning of every field of mcle_mimo_pilot_cfg and of every pointer
+ * are those of mcle_run_mimo_pilot_link; d_counters[0] / row 0 of d_sym_err, d_bit_err [2][count]: estimated CSI, [1]: perfect CSI;
+ * d_err, d_pow f64.  When d_chan_factor is NULL, H = alpha W with no product by an identity matrix.
+ * What differs from mcle_run_mimo_pilot_link is the envelope and the machinery: 1 <= nt <= 8, nt <= nr <= 16 (d_chan_factor and
+ * d_mmse_matrix [nr][nr] accordingly), nt <= n_pilots <= 256, n_symbols >= 1 with nr * n_symbols <= 2^31 - 1, noise_var >= 0 and
+ * finite, pilot_power > 0, alpha finite, the MMSE estimator needs nt = 1 and d_mmse_matrix, fixed pilots need d_pilots,
+ * count <= 2^31 - 1.  Anything else: MCLE_E_INVAL with a message naming the rule, nothing touched; count = 0 returns MCLE_OK and
+ * launches nothing.  The set-up (always f64) takes one realization per row of 16 lanes, a lane per receive antenna; the walk is
+ * that of mcle_run_mimo_large on the matrix cores with two left operands, every symbol and noise sample drawn once for both.
+ * The draw ledger is the pilot link's, word for word (CHAN r nt + a, DATA t nt + a, NOISE r n_symbols + t, PHASE a n_pilots + p,
+ * PILOT 2 ceil(n_pilots / 2) r + p), so up to 4 x 4 this entry point runs the realizations of mcle_run_mimo_pilot_link, and with
+ * L = I and alpha = 1 block 1 runs those of mcle_run_mimo_large at every shape (the perfect-CSI record is bit-identical to the
+ * one k_mimo_large_setup writes).  Nothing depends on the grid, on MCLE_OPT_GRID_OVERSUB or on how [first, first + count) is
+ * split.  Device memory: two records of mcle_run_mimo_large's length per realization (at most 12 KiB at 8 x 16 in complex128) in
+ * the context's scratch buffer, launch slices of at most 128 MiB.
+ * mcle_ctx_last_kernel: "mimo_large_pilot_link f64|f32 <nr>x<nt> s<K-steps> ls|mmse". */
+int mcle_run_mimo_large_pilot(mcle_ctx* ctx, int dtype, const mcle_mimo_pilot_cfg* cfg, uint64_t seed, uint64_t first,
+                              uint64_t count, const double* d_pilots, const double* d_chan_factor, const double* d_mmse_matrix,
+                              mcle_counters* d_counters, uint32_t* d_sym_err, uint32_t* d_bit_err, double* d_err, double* d_pow);
 
 /* ---- Grassmannian codebooks: chordal distances and the random search (subspace/metrics.py:21-113 calc_principal_angles,
  *      calc_chordal_distance_from_principal_angles; apps/find_codebook.py:73-231 CodebookFinder) ---------------------------

@@ -312,6 +312,8 @@ _PROTOS = {
     "mcle_run_pilot_mse": (c_int, [_P, c_int, POINTER(PilotMseCfg), c_uint64, c_uint64, c_uint64, _P, _P, _P]),
     "mcle_run_mimo_pilot_link": (c_int, [_P, c_int, POINTER(MimoPilotCfg), c_uint64, c_uint64, c_uint64, _P, _P, _P, _P, _P, _P, _P,
                                          _P]),
+    "mcle_run_mimo_large_pilot": (c_int, [_P, c_int, POINTER(MimoPilotCfg), c_uint64, c_uint64, c_uint64, _P, _P, _P, _P, _P, _P, _P,
+                                          _P]),
     "mcle_chordal_min_dist": (c_int, [_P, c_int, _P, c_size_t, c_int, c_int, c_int, _P, _P, _P]),
     "mcle_codebook_generate": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_uint64, c_uint64, c_uint64, _P]),
     "mcle_run_codebook_search": (c_int, [_P, c_int, POINTER(CodebookCfg), c_uint64, c_uint64, c_uint64, POINTER(CodebookResult),

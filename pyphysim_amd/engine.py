@@ -1588,6 +1588,22 @@ class Engine:
         estimate and from H (mmse=True: set_noise_var(noise_var)), n_symbols per layer.  Returns (counters with estimated
         CSI, counters with perfect CSI); with per_realization=True also sym_err [2, count], bit_err [2, count] (row 0
         estimated, row 1 perfect; 0xFFFFFFFF marks a skipped realization), err [count] = |H^ - H|_F^2, pow [count] = |H|_F^2."""
+        return self._pilot_link(self.lib.mcle_run_mimo_pilot_link, nt, nr, n_pilots, n_symbols, noise_var, seed, first, count,
+                                pilot_power, alpha, pilots, chan_factor, cov, estimator, mmse, method, dtype, per_realization)
+
+    def run_mimo_large_pilot_link(self, nt, nr, n_pilots, n_symbols, noise_var, seed, first, count, pilot_power=1.0, alpha=1.0,
+                                  pilots=None, chan_factor=None, cov=None, estimator="ls", mmse=False, method=DEMOD_MINDIST,
+                                  dtype=None, per_realization=False):
+        """run_mimo_pilot_link for large arrays (mcle_run_mimo_large_pilot): 1 <= nt <= 8, nt <= nr <= 16, the walk of
+        run_mimo_large on the matrix cores through the filter of the estimate and that of the channel at once.  Same
+        arguments, same return value, same draws: up to 4 x 4 the realizations of run_mimo_pilot_link, and with no chan_factor
+        and alpha = 1 the perfect-CSI block is run_mimo_large on the same (seed, first, count)."""
+        return self._pilot_link(self.lib.mcle_run_mimo_large_pilot, nt, nr, n_pilots, n_symbols, noise_var, seed, first, count,
+                                pilot_power, alpha, pilots, chan_factor, cov, estimator, mmse, method, dtype, per_realization)
+
+    def _pilot_link(self, entry, nt, nr, n_pilots, n_symbols, noise_var, seed, first, count, pilot_power, alpha, pilots,
+                    chan_factor, cov, estimator, mmse, method, dtype, per_realization):
+        """The call both pilot links share: `entry` is the library's entry point."""
         dt = self._dt(dtype)
         nt, nr, P, count = int(nt), int(nr), int(n_pilots), int(count)
         if estimator not in _lib.PILOT_ESTIMATORS:
@@ -1614,7 +1630,7 @@ class Engine:
         if per_realization:
             se, be = self.empty((2, count), np.uint32), self.empty((2, count), np.uint32)
             err, pw = self.empty(count, np.float64), self.empty(count, np.float64)
-        self._raise_value(self.lib.mcle_run_mimo_pilot_link(
+        self._raise_value(entry(
             self.ctx, dt, byref(cfg), int(seed), int(first), count, d_p.ptr if d_p is not None else None,
             d_L.ptr if d_L is not None else None, d_B.ptr if d_B is not None else None, cnt.ptr,
             se.ptr if per_realization else None, be.ptr if per_realization else None,

@@ -632,10 +632,14 @@ class PilotMimoSimulator(_LinkSimulator):
                      ("random_pilots", bool(random_pilots)), ("mmse", bool(mmse))):
             self.params.add(k, v)
 
+    @staticmethod
+    def _entry(eng):
+        return eng.run_mimo_pilot_link
+
     def _launch(self, current_parameters, first_rep, count, per_realization):
         p = current_parameters
         eng = self._bind()
-        c_est, c_perf, se, be, err, pw = eng.run_mimo_pilot_link(
+        c_est, c_perf, se, be, err, pw = self._entry(eng)(
             p["Nt"], p["Nr"], p["num_pilots"], p["NSymbs"], self._noise_var(p), self._seed_for(p), first_rep, count,
             pilot_power=p["pilot_power"], alpha=p["alpha"], pilots=self._pilots, chan_factor=self._L,
             cov=self._cov if p["estimator"] == "mmse" else None, estimator=p["estimator"], mmse=p["mmse"],
@@ -667,6 +671,23 @@ class PilotMimoSimulator(_LinkSimulator):
         res.add_result(Result.from_batch("mse", Result.RATIOTYPE, err, norm * m, err / norm, float(c.get("err_sq", 0.0)) / norm ** 2, m))
         res.add_result(Result.from_batch("channel_power", Result.RATIOTYPE, pw, float(m), pw, float(c.get("pow_sq", 0.0)), m))
         return res
+
+
+class LargePilotMimoSimulator(PilotMimoSimulator):
+    """PilotMimoSimulator for large arrays: 1 <= Nt <= 8, Nt <= Nr <= 16 (the envelope of LargeMimoSimulator), one call of
+    Engine.run_mimo_large_pilot_link per batch -- how many pilots a large receive array needs before the estimate stops costing
+    symbol errors.  Same constructor, same results ('ber', 'ser', 'ber_perfect_csi', 'ser_perfect_csi', 'mse', 'channel_power'
+    and the limb sums), same draws: up to 4 x 4 the counts of PilotMimoSimulator, and without a covariance and with alpha = 1
+    'ser_perfect_csi' is LargeMimoSimulator's 'ser' on the same seed."""
+
+    def __init__(self, SNR, Nr=16, Nt=4, num_pilots=8, **kw):
+        if not (1 <= int(Nt) <= 8 and int(Nt) <= int(Nr) <= 16):
+            raise ValueError("LargePilotMimoSimulator needs 1 <= Nt <= 8 and Nt <= Nr <= 16 (got Nt %d, Nr %d)" % (Nt, Nr))
+        super().__init__(SNR, Nr=Nr, Nt=Nt, num_pilots=num_pilots, **kw)
+
+    @staticmethod
+    def _entry(eng):
+        return eng.run_mimo_large_pilot_link
 
 
 class CompSimulator(BatchedSimulationRunner):
