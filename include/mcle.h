@@ -401,7 +401,16 @@ int mcle_blast_encode(mcle_ctx* ctx, int dtype, const void* d_x, int nt, size_t 
                       size_t batch);
 /* G = sqrt(nt) * solve(H^H H + noise_var I, H^H) per batch item (noise_var = 0: ZF / pinv for
  * full column rank); d_H [batch, nr, nt] row-major, d_G [batch, nt, nr]; d_skipped[batch]
- * flags singular systems (may be NULL). */
+ * (may be NULL) is 1 iff A = H^H H + noise_var I is numerically rank deficient in the CALL's
+ * arithmetic, and then G means nothing: some Cholesky pivot is <= tol * A[j][j] (or not a number),
+ * tol = 2^-42 for MCLE_F64 and 2^-34 for MCLE_F32 (a complex64 H is a rank-deficient one moved by
+ * eps32).  pivot_j / A[j][j] >= 1 / cond(A), so a channel with cond(H) <= 1e6 (MCLE_F64) or <= 1e2
+ * (MCLE_F32) is never flagged at noise_var = 0, and none with noise_var >= 2 tol nr max|h|^2.
+ * Accuracy: the MMSE filter is within a small multiple of NumPy's solve at the same dtype.  The ZF
+ * filter comes from the normal equations, not from a pseudo-inverse, so it may lose ONE more power
+ * of the condition number than numpy.linalg.pinv at the same dtype and no more:
+ * |G - G_exact|_max <= 8 cond(H) max(|pinv_dtype - G_exact|_max, eps_dtype |G_exact|_max).
+ * Magnitudes: the squared column norms must stay inside the double range (|h| from 1e-150 to 1e150). */
 int mcle_blast_filter(mcle_ctx* ctx, int dtype, const void* d_H, int nr, int nt,
                       double noise_var, void* d_G, uint32_t* d_skipped, size_t batch);
 /* est[c*nt + a] = sum_r G[a, r] Y[r, c]      (decode, :658-660) */
@@ -433,14 +442,25 @@ int mcle_mrt_encode(mcle_ctx* ctx, int dtype, const void* d_h, const void* d_x, 
 int mcle_mrt_decode(mcle_ctx* ctx, int dtype, const void* d_h, const void* d_y, int nt, size_t n,
                     void* d_out, size_t batch);
 /* SVDMimo (mimo.py:833-946), square H [batch][n][n]: W = V/sqrt(n) (precoder), G = diag(1/S) U^H sqrt(n)
- * (receive filter), S descending (d_S may be NULL).  encode = W @ x.reshape(n,-1), decode = G @ Y via
- * mcle_mimo_channel. */
+ * (receive filter), S descending (d_S may be NULL, always double).  encode = W @ x.reshape(n,-1), decode = G @ Y
+ * via mcle_mimo_channel.  One-sided Jacobi in f64 for both dtypes; every threshold is relative, so H times a power of
+ * two gives S times it, the same W bit for bit and G divided by it.  Supported magnitudes: 1e-150 < |h| < 1e150 --
+ * the routine works on squared column norms, which underflow or overflow outside that range and then S is silently
+ * wrong; scale such channels first.  No flag: a zero singular value gives a row of G that is not finite (diag(1/S),
+ * as the reference), S, W and the other rows of G stay valid. */
 int mcle_svd_filters(mcle_ctx* ctx, int dtype, const void* d_H, int n_ant, void* d_W, void* d_G,
                      double* d_S, size_t batch);
 
 /* GMDMimo (mimo.py:952-1067) + util.misc.gmd (misc.py:18-159), square H: W = P/sqrt(n), G = Blast filter
  * (ZF for noise_var = 0, else MMSE) on the equivalent channel Q R; d_R [batch][n][n] (real upper
- * triangular with constant diagonal; may be NULL). */
+ * triangular with constant diagonal; may be NULL).  d_skipped[batch] (may be NULL) is 1 iff H is numerically rank
+ * deficient in the call's arithmetic, and then W, G and R mean nothing: sigma_min <= sqrt(tol) sigma_max (the
+ * decomposition divides by the geometric mean of the singular values whatever noise_var is), or the filter's system
+ * Heq^H Heq + noise_var I is flagged as in mcle_blast_filter (the same tol, the same Cholesky and the same ZF accuracy
+ * contract, on Heq = Q R).  So cond(H) <= 1e6 (MCLE_F64) / 1e2 (MCLE_F32) is never flagged.  With a repeated singular
+ * value or one AT the geometric mean R is one of several valid factors (the rotation is 0/0 and is skipped or taken at
+ * an arbitrary angle): triangular, constant diagonal, Q and P unitary hold, the entries are not unique.  Magnitudes as
+ * mcle_svd_filters, and the product of the singular values must stay inside the double range. */
 int mcle_gmd_filters(mcle_ctx* ctx, int dtype, const void* d_H, int n_ant, double noise_var, void* d_W,
                      void* d_G, double* d_R, uint32_t* d_skipped, size_t batch);
 /* calc_post_processing_linear_SINRs (mimo/mimo.py:62-118; MimoBase.calc_linear_SINRs :311-345): complex128

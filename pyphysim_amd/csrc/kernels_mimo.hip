@@ -9,6 +9,15 @@ namespace mcle {
 
 constexpr int kMimoBlock = 256;
 
+// Rank-deficiency tolerance of mcle_blast_filter / mcle_gmd_filters on pivot_j / A[j][j] (mimo.hpp, blast_filter_t<REL>): a
+// channel is flagged iff it is rank deficient in the arithmetic of the CALL.  complex128: 2^-42 = 1024 eps -- the residue of
+// an exactly dependent column is some 10 eps of its diagonal entry (up to 200 eps seen with other orders of the same
+// operations), a channel of cond 1e6 keeps every pivot above 1 / cond^2 = 4500 eps (tests/test_mimo_ops_oracle_cpu.py records the separation).  complex64: the matrix arrives
+// rounded to 24 bits, which leaves a dependent column a relative distance of about eps32 from the span of the others, i.e.
+// a pivot ratio of about eps32^2; 2^-34 = (64 eps32)^2, where cond 1e2 keeps 1e-4.  (The elimination itself runs in f64
+// for both.)  mcle_gmd_filters applies the square root of the same number to sigma_min / sigma_max.
+template <typename T> constexpr double kRankTol = sizeof(T) == 4 ? 0x1p-34 : 0x1p-42;
+
 // X[b][a][c] = x[b][c*nt + a] / sqrt(nt)
 template <typename T>
 __global__ __launch_bounds__(kMimoBlock) void k_blast_encode(const cx<T>* __restrict__ x, int nt, size_t ns,
@@ -59,7 +68,7 @@ __global__ __launch_bounds__(64) void k_blast_filter(const cx<T>* __restrict__ H
                 const cx<T> v = Hg[(b * NR + r) * NT + a];
                 H[r][a] = mk<double>((double)v.x, (double)v.y);
             }
-        const bool ok = blast_filter<NT, NR>(H, nv, G);
+        const bool ok = blast_filter_rel<NT, NR>(H, nv, G, kRankTol<T>);
 #pragma unroll
         for (int a = 0; a < NT; ++a)
 #pragma unroll
@@ -111,7 +120,7 @@ __global__ __launch_bounds__(64) void k_blast_filter_staged(const cx<T>* __restr
         for (int r = 0; r < NR; ++r)
 #pragma unroll
             for (int a = 0; a < NT; ++a) H[r][a] = mk<double>((double)hm[r * NT + a].x, (double)hm[r * NT + a].y);
-        const bool ok = blast_filter<NT, NR>(H, nv, G);
+        const bool ok = blast_filter_rel<NT, NR>(H, nv, G, kRankTol<T>);
         cx<T> gm[E];
 #pragma unroll
         for (int a = 0; a < NT; ++a)
@@ -546,7 +555,7 @@ __global__ __launch_bounds__(64) void k_gmd_filters(const cx<T>* __restrict__ Hg
                 const cx<T> v = Hg[(b * NA + r) * NA + c];
                 H[r][c] = mk<double>((double)v.x, (double)v.y);
             }
-        const bool ok = gmd_filters_dev<NA>(H, nv, W, G, R);
+        const bool ok = gmd_filters_dev<NA, true>(H, nv, W, G, R, kRankTol<T>);
 #pragma unroll
         for (int r = 0; r < NA; ++r)
 #pragma unroll

@@ -14,8 +14,14 @@ namespace mcle {
 // H: NR x NT (row-major), G: NT x NR.  Returns false if H^H H + nv I is not positive definite.
 // R = double everywhere one filter serves a whole realization; R = float only where a filter is needed per
 // subcarrier (frequency-selective pipeline, f32 instantiation).
-template <typename R, int NT, int NR>
-__device__ __forceinline__ bool blast_filter_t(const cx<R> (&H)[NR][NT], R nv, cx<R> (&G)[NT][NR]) {
+// REL = false (the fused links): a pivot fails when it is <= an absolute floor, i.e. only when the cancellation in the
+// Cholesky step happens to be exact (H = ones) -- a random rank-deficient H leaves a pivot of a few eps of its diagonal
+// entry, of either sign, and about half of those pass.  REL = true (the operator kernels k_blast_filter(_staged) and
+// k_gmd_filters): pivot j fails when it is <= rel_tol * A[j][j], A = H^H H + nv I.  pivot_j / A[j][j] is the squared sine
+// of the angle between column j of [H; sqrt(nv) I] and the span of the columns before it: unchanged by scaling H or any
+// of its columns, >= 1 / cond(A), and a few eps for a column that lies in that span.
+template <typename R, int NT, int NR, bool REL = false>
+__device__ __forceinline__ bool blast_filter_t(const cx<R> (&H)[NR][NT], R nv, cx<R> (&G)[NT][NR], R rel_tol = (R)0) {
     typedef cx<R> C;
     C L[NT][NT];  // lower Cholesky factor of A = H^H H + nv I (strict upper part unused)
     R invd[NT];   // 1 / L[j][j]
@@ -29,10 +35,13 @@ __device__ __forceinline__ bool blast_filter_t(const cx<R> (&H)[NR][NT], R nv, c
             for (int r = 0; r < NR; ++r) a = cadd(a, cmulc(H[r][j], H[r][i]));  // conj(H[r][i]) * H[r][j]
             // a = A[i][j]
             if (i == j) a.x += nv;
+            const R ajj = a.x;   // (i == j: the diagonal entry before the elimination)
 #pragma unroll
             for (int k = 0; k < j; ++k) a = csub(a, cmulc(L[i][k], L[j][k]));
             if (i == j) {
-                ok = ok && (a.x > (R)(sizeof(R) == 8 ? 1e-300 : 1e-30));
+                R least = (R)(sizeof(R) == 8 ? 1e-300 : 1e-30);
+                if constexpr (REL) least = fmax(least, rel_tol * ajj);
+                ok = ok && (a.x > least);   // (a NaN pivot fails too)
                 L[j][j] = mk<R>(sqrt(a.x), (R)0);
                 invd[j] = (R)1 / L[j][j].x;
             } else {
@@ -269,6 +278,11 @@ __device__ __forceinline__ bool blast_solve_gram(const cx<R> (&A)[NT][NT], R nv,
 template <int NT, int NR>
 __device__ __forceinline__ bool blast_filter(const double2 (&H)[NR][NT], double nv, double2 (&G)[NT][NR]) {
     return blast_filter_t<double, NT, NR>(H, nv, G);
+}
+// the operator kernels' form: relative pivot test (see blast_filter_t)
+template <int NT, int NR>
+__device__ __forceinline__ bool blast_filter_rel(const double2 (&H)[NR][NT], double nv, double2 (&G)[NT][NR], double rel_tol) {
+    return blast_filter_t<double, NT, NR, true>(H, nv, G, rel_tol);
 }
 
 }  // namespace mcle

@@ -123,9 +123,12 @@ __device__ __forceinline__ void svd_filters_dev(double2 (&A)[NA][NA], double2 (&
 // a constant diagonal (the geometric mean of the singular values).  W = P / sqrt(Nt); the receive filter
 // is Blast's (ZF / MMSE) on the equivalent channel Q R.  R depends on S only and is reproduced exactly;
 // Q and P inherit the SVD's phase freedom.
-template <int NA>
+// REL = true (the operator kernel): the channel is also reported when its smallest singular value is <= sqrt(rel_tol)
+// times the largest (the decomposition divides by the geometric mean of all of them, whatever noise_var is), and the
+// filter takes blast_filter_t's relative pivot test; REL = false (the fused link) keeps the absolute pivot floor alone.
+template <int NA, bool REL = false>
 __device__ __forceinline__ bool gmd_filters_dev(const double2 (&Hin)[NA][NA], double nv, double2 (&W)[NA][NA],
-                                                double2 (&G)[NA][NA], double (&R)[NA][NA]) {
+                                                double2 (&G)[NA][NA], double (&R)[NA][NA], double rel_tol = 0.0) {
     double2 Q[NA][NA], P[NA][NA];
     double d[NA], z[NA];
 #pragma unroll
@@ -136,6 +139,8 @@ __device__ __forceinline__ bool gmd_filters_dev(const double2 (&Hin)[NA][NA], do
             R[r][c] = 0.0;
         }
     jacobi_svd<NA>(Q, P, d);
+    bool full_rank = true;
+    if constexpr (REL) full_rank = d[NA - 1] > sqrt(rel_tol) * d[0];   // (false for a NaN too)
 #pragma unroll
     for (int c = 0; c < NA; ++c) {  // Q <- U
         z[c] = 0.0;
@@ -145,7 +150,13 @@ __device__ __forceinline__ bool gmd_filters_dev(const double2 (&Hin)[NA][NA], do
     double prod = 1.0;
 #pragma unroll
     for (int c = 0; c < NA; ++c) prod *= d[c];
-    const double sigma_bar = pow(prod, 1.0 / NA);
+    // REL: the root by sqrt / cbrt -- pow() of a product near 2^+-160 (a channel scaled by 2^+-40) was 5 ulp off, which the
+    // rotation's (sigma_bar^2 - d2^2) / (d1^2 - d2^2) amplified to 600 eps in R; the fused link keeps its bits
+    double sigma_bar;
+    if constexpr (REL && NA == 2) sigma_bar = sqrt(prod);
+    else if constexpr (REL && NA == 3) sigma_bar = cbrt(prod);
+    else if constexpr (REL && NA == 4) sigma_bar = sqrt(sqrt(prod));
+    else sigma_bar = pow(prod, 1.0 / NA);
     int perm[NA], invperm[NA];
 #pragma unroll
     for (int c = 0; c < NA; ++c) perm[c] = invperm[c] = c;
@@ -242,7 +253,9 @@ __device__ __forceinline__ bool gmd_filters_dev(const double2 (&Hin)[NA][NA], do
             for (int m = 0; m < NA; ++m) acc = cadd(acc, cscale(Q[r][m], R[m][c]));
             Heq[r][c] = acc;
         }
-    const bool ok = blast_filter<NA, NA>(Heq, nv, G);
+    bool ok;
+    if constexpr (REL) ok = blast_filter_rel<NA, NA>(Heq, nv, G, rel_tol) && full_rank;
+    else ok = blast_filter<NA, NA>(Heq, nv, G);
     const double root = sqrt((double)NA);
 #pragma unroll
     for (int r = 0; r < NA; ++r)

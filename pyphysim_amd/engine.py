@@ -104,6 +104,10 @@ class Engine:
         check(self.lib.mcle_ctx_device_info(self.ctx, byref(n_cu), byref(lds), name, 128))
         self.n_cu, self.device_name = n_cu.value, name.value.decode()
 
+    def device_info(self):
+        """{'n_cu': compute units, 'name': device name} of this engine's device."""
+        return {"n_cu": self.n_cu, "name": self.device_name}
+
     def _alloc(self, nbytes):
         free = self._pool.get(nbytes)
         if free:
@@ -656,8 +660,10 @@ class Engine:
         self._raise_value(self.lib.mcle_svd_filters(self.ctx, dt, d_H.ptr, n, W.ptr, G.ptr, S.ptr, b))
         return self._out(W, host), self._out(G, host), S.get()
 
-    def gmd_filters(self, H, noise_var=0.0, dtype=None):
-        """H [batch, n, n] -> (W precoder, G receive filter, R [batch, n, n] real upper triangular)."""
+    def gmd_filters(self, H, noise_var=0.0, dtype=None, return_skipped=False):
+        """H [batch, n, n] -> (W precoder, G receive filter, R [batch, n, n] real upper triangular); with return_skipped
+        also skipped [batch] (uint32: 1 where the channel is rank deficient in the call's arithmetic and W, G, R mean
+        nothing -- include/mcle.h at mcle_gmd_filters)."""
         dt = self._dt(dtype)
         d_H, host = self._cin(H, dt)
         b, n, _n = d_H.shape
@@ -665,6 +671,8 @@ class Engine:
         R, sk = self.empty((b, n, n), np.float64), self.empty(b, np.uint32)
         self._raise_value(self.lib.mcle_gmd_filters(self.ctx, dt, d_H.ptr, n, float(noise_var), W.ptr, G.ptr, R.ptr,
                                                     sk.ptr, b))
+        if return_skipped:
+            return self._out(W, host), self._out(G, host), R.get(), sk.get()
         return self._out(W, host), self._out(G, host), R.get()
 
     def post_processing_sinrs(self, H, W, G_H, noise_var):
