@@ -479,7 +479,13 @@ int mcle_post_processing_sinrs(mcle_ctx* ctx, const void* d_H, const void* d_W, 
  * precoder in the top-left corner (nt[j] x ns[j], or (sum nt) x ns[j] when `joint`); d_U [batch][K][4][4]
  * (nr[k] x ns[k], may be NULL).  Outputs (each may be NULL), zero padded: d_Q [batch][K][4][4] interference from
  * the other users + Re_k; d_Re [batch][K][4][4] = pe ext ext^H + noise_var I; d_B [batch][K][4][4][4] (stream l:
- * everything received minus stream l's own covariance); d_sinr [batch][K][4] (linear). */
+ * everything received minus stream l's own covariance); d_sinr [batch][K][4] (linear).
+ * Edges: a user with ns[k] = 0 contributes nothing and gets zero B / sinr rows; d_F may be NULL only when no user has
+ * streams; d_sinr needs d_U; a zero path-loss entry removes that link exactly; noise_var = 0 and n_ext = 0 give Re = 0
+ * exactly; a refused call and batch = 0 write nothing.  Accuracy: every entry is within c eps of its MAGNITUDE (the
+ * same formula on absolute values), c the length of the accumulation chain (81 for Q at sum Nt = 16 in joint mode with a path loss);
+ * B_kl = (sum) - g g^H is formed by subtraction, so where one stream dominates it is accurate relative to the sum, not
+ * to the difference.  tests/test_gpu_multiuser_envelope.py holds this against a 50-digit oracle. */
 typedef struct mcle_mu_stats_cfg {
     int32_t K;                  /* users (with receive antennas), <= 4 */
     int32_t n_ext;              /* external interferer antennas: trailing columns of big_H, <= 8 */
@@ -703,7 +709,29 @@ int mcle_ia_iterative(mcle_ctx* ctx, int solver, int initialize_with, const void
  *      Outputs, zero padded: d_Ms [batch][K][K r][r] (user k's precoder MsPk, K r x Ns), d_W [batch][K][r][r]
  *      (receive filter, Ns x r), d_ns [batch][K]; d_cand_sinr [batch][K][r][r] (metric 4 only: row ns-1 = the
  *      post-filter SINRs with ns streams, EnhancedBD._calc_linear_SINRs :1101-1138, for caller-side metrics such
- *      as 'effective_throughput').  Singular-vector phases are ours (see mcle_block_diagonalize). */
+ *      as 'effective_throughput').  Singular-vector phases are ours (see mcle_block_diagonalize).
+ *      d_skipped [batch] (may be NULL) is 1 iff the channel of the K users is numerically singular, or -- WhiteningBD
+ *      only -- some Re_k is: an eigenvalue of Re_k <= 2^-42 of its largest (mcle_blast_filter's tolerance; relative, so
+ *      big_H times a power of two flags the same items; a rank-deficient pe H_ext H_ext^H at noise_var = 0 comes out
+ *      of the Jacobi sweep at about 1e-17 of the largest, not at 0).  The outputs of a flagged item mean nothing.
+ *      Receive filters: W_k = pinv(H_k Ms_k) (None; times the whitening filter for WhiteningBD) goes through the
+ *      Jacobi pseudo-inverse and loses ONE power of cond(H_k Ms_k), as numpy.linalg.pinv does; W_k H_k Ms_k = I to
+ *      eps ||W_k|| ||H_k|| ||Ms_k||.
+ *      Repeated eigenvalues of Re_k (decided here, not in the reference):
+ *      - pe = 0 or n_ext = 0: Re_k = noise_var I, V = I, and the cut V[:, :ns] keeps the FIRST ns block-diagonalising
+ *        directions (those with the smallest singular values of H_k Ms_k): 'fixed' and the per-user rule then return
+ *        bit for bit what 'naive' returns for ns < r.
+ *      - rank(H_ext,k) < r - ns: the cut lies inside the noise eigenspace, in the basis the Jacobi sweep leaves; any
+ *        basis is a valid answer, and every one has W_k H_ext,k = 0, W_k H_k MsPk = I, ||MsPk||_F^2 = iPu.
+ *      - the whitening filter is V diag(L^-1/2) with ORTHONORMAL V in every case, so the whitened equivalent channels
+ *        are orthogonal; the reference's numpy.linalg.eig returns a non-orthogonal basis of a repeated eigenvalue's
+ *        space, for which its filter does not whiten (Ms Ms^H, W^H W and |W H_k Ms| are the same either way).
+ *      - noise_var = pe = 0 (EnhancedBD only; WhiteningBD is refused or flagged): Re_k = 0, the one-stream candidate
+ *        has an infinite SINR (d_cand_sinr holds +inf) and, the first maximum deciding, 'capacity' returns Ns = 1.
+ *        With noise_var = 0 and pe > 0 a candidate whose cut lies in the null space of Re_k has an infinite exact SINR
+ *        and a computed one that is a rounding residue: the selection among such candidates is the
+ *        first maximum of those residues.
+ *      Held to a 50-digit oracle over every geometry with K r <= 8 by tests/test_gpu_bd_extint_envelope.py. */
 typedef struct mcle_bd_extint_cfg {
     int32_t num_users, n_ant_per_user, n_ext;
     int32_t method;             /* 0: WhiteningBD, 1: EnhancedBD */

@@ -64,8 +64,11 @@ def bd_no_power_scaling(H, K):
     for user in range(K):
         others = [i for u in range(K) if u != user for i in _user_rows(K, nr, u)]
         tilde_H = H[others, :]
-        n_streams = nr - np.linalg.matrix_rank(tilde_H)
-        tilde_V0 = least_right_singular_vectors(tilde_H, n_streams)[0]
+        if K == 1:                                            # a single user: nothing to avoid
+            n_streams, tilde_V0 = nr, np.eye(H.shape[1], dtype=complex)
+        else:
+            n_streams = nr - np.linalg.matrix_rank(tilde_H)
+            tilde_V0 = least_right_singular_vectors(tilde_H, n_streams)[0]
         _, V1, S = least_right_singular_vectors(H[_user_rows(K, nr, user), :] @ tilde_V0, r - n_streams)
         Ms.append(tilde_V0 @ V1)
         Sigma.extend(S)

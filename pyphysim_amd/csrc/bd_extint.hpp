@@ -336,6 +336,20 @@ __device__ __forceinline__ bool bd_extint_lane(const BdExtParams& pp, const cd* 
                 Re[i * r + j] = acc;
             }
     };
+    // W [r x r] = pinv(G_k MsPk), G_k = rows of user k of G [n x n].  The columns of G_k MsPk are orthogonal only up to
+    // eps |G_k| |MsPk|, which against a small column is eps cond^2: the conjugate-transpose shortcut of bd_receive_filter
+    // left W G_k MsPk = I off by that much (0.5 at cond 1e8), so the block goes through the Jacobi pseudo-inverse, which
+    // loses one power of the condition number as numpy.linalg.pinv does.
+    auto own_block_pinv = [&](const cd* G, int k, const cd* MsPk, cd* W) {
+        cd E[kBdMaxR * kBdMaxR];
+        for (int i = 0; i < r; ++i)
+            for (int c = 0; c < r; ++c) {
+                cd acc = mk<double>(0, 0);
+                for (int m = 0; m < n; ++m) acc = cadd(acc, cmul(G[(k * r + i) * n + m], MsPk[m * r + c]));
+                E[i * r + c] = acc;
+            }
+        bd_pinv_small(E, r, r, W);
+    };
     if (pp.method == 0) {
         // WhiteningBD: whiten every user's rows with W_k^H = diag(L^-1/2) V^H of eig(Re_k), block-diagonalise the
         // whitened channel, receive filter = pinv(newH) x whitening filter (:781-836)
@@ -346,9 +360,14 @@ __device__ __forceinline__ bool bd_extint_lane(const BdExtParams& pp, const cd* 
             double w[kBdMaxR];
             cov(k, Re);
             bd_heig_psd(Re, r, w, V);
+            // Re_k is numerically singular when an eigenvalue is <= 2^-42 of the largest (w ascends): Jacobi returns
+            // about 1e-17 w_max, not 0, for a rank-deficient covariance, and 1 / sqrt of that means nothing.  Relative,
+            // so big_H times a power of two flags the same lanes (mcle_blast_filter's rule and tolerance).
+            const double floor_w = 0x1p-42 * w[r - 1];
             for (int i = 0; i < r; ++i) {
-                ok = ok && w[i] > 0.0;
-                const double s = 1.0 / sqrt(w[i] > 0.0 ? w[i] : 1.0);
+                const bool pos = w[i] > floor_w && w[i] > 0.0;
+                ok = ok && pos;
+                const double s = 1.0 / sqrt(pos ? w[i] : 1.0);
                 for (int j = 0; j < r; ++j) Wf[k][i * r + j] = cscale(cconj(V[j * r + i]), s);
             }
             for (int i = 0; i < r; ++i)
@@ -359,15 +378,15 @@ __device__ __forceinline__ bool bd_extint_lane(const BdExtParams& pp, const cd* 
                 }
         }
         ok = bd_solve(Heq, K, r, pp.iPu, pp.nv, 0, Q, L, Ms, sigma) && ok;
-        bd_receive_filter(Heq, Ms, K, r, Q);                 // pinv(newH), block diagonal
         for (int k = 0; k < K; ++k) {
-            cd MsPk[kBdMaxN * kBdMaxR], W[kBdMaxR * kBdMaxR];
+            cd MsPk[kBdMaxN * kBdMaxR], W[kBdMaxR * kBdMaxR], Pi[kBdMaxR * kBdMaxR];
             for (int m = 0; m < n; ++m)
                 for (int c = 0; c < r; ++c) MsPk[m * r + c] = Ms[m * n + k * r + c];
+            own_block_pinv(Heq, k, MsPk, Pi);                // pinv(newH)'s block of user k
             for (int i = 0; i < r; ++i)
                 for (int c = 0; c < r; ++c) {
                     cd acc = mk<double>(0, 0);
-                    for (int j = 0; j < r; ++j) acc = cadd(acc, cmul(Q[(k * r + i) * n + k * r + j], Wf[k][j * r + c]));
+                    for (int j = 0; j < r; ++j) acc = cadd(acc, cmul(Pi[i * r + j], Wf[k][j * r + c]));
                     W[i * r + c] = acc;
                 }
             emit(k, MsPk, W, r);
@@ -375,13 +394,11 @@ __device__ __forceinline__ bool bd_extint_lane(const BdExtParams& pp, const cd* 
     } else if (pp.metric == 0) {
         // EnhancedBD without a metric: plain BD, every user inverts its own block (:1140-1195)
         ok = bd_solve(H, K, r, pp.iPu, pp.nv, 0, Q, L, Ms, sigma);
-        bd_receive_filter(H, Ms, K, r, Q);
         for (int k = 0; k < K; ++k) {
             cd MsPk[kBdMaxN * kBdMaxR], W[kBdMaxR * kBdMaxR];
             for (int m = 0; m < n; ++m)
                 for (int c = 0; c < r; ++c) MsPk[m * r + c] = Ms[m * n + k * r + c];
-            for (int i = 0; i < r; ++i)
-                for (int c = 0; c < r; ++c) W[i * r + c] = Q[(k * r + i) * n + k * r + c];
+            own_block_pinv(H, k, MsPk, W);
             emit(k, MsPk, W, r);
         }
     } else {
