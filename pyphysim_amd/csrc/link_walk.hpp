@@ -1,8 +1,8 @@
 // link_walk.hpp -- what the record-walking link kernels share.  A workgroup of four independent wavefronts walks the symbol
 // columns of chunks of realizations, a realization's coefficients coming from the record a set-up kernel wrote:
-// k_mimo_flat_link, k_mimo_pilot_link, k_mimo_large_link, k_ia_link, k_bd_link, k_comp_link, k_iagl_link.  A new link of
-// this kind brings its estimate arithmetic and its record layout; the prologue, the draws (wave_draws.hpp), the decisions and
-// the per-realization tail are here.
+// k_mimo_flat_link, k_mimo_pilot_link, k_mimo_large_link, k_mimo_large_pilot_link (those two share their whole walk:
+// mimo_large_link.hpp), k_ia_link, k_bd_link, k_comp_link, k_iagl_link.  A new link of this kind brings its estimate arithmetic
+// and its record layout; the prologue, the draws (wave_draws.hpp), the decisions and the per-realization tail are here.
 //
 // The decision form of these walks is a RUN-TIME property of the launch (the demodulation method and the constellation pick it
 // inside one compiled kernel).  walk_f64.hpp is the other kind: the packed walk, walk_decide<T, DEC, N> with the form a

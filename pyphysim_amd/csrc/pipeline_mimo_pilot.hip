@@ -21,13 +21,10 @@
 //     pilot phase (a, p)    PHASE (3)   uniform a P + p                         random pilots only
 //     pilot noise (r, p)    PILOT (4)   CN sample 2 ceil(P / 2) r + p           (a Philox block = pilots 2 j, 2 j + 1 of one antenna)
 // With L = I and alpha = 1 counter block 1 is mcle_run_mimo_flat(MCLE_MIMO_BLAST) on the same (seed, realization).
-#include <cmath>
-#include <complex>
-#include <vector>
-
 #include "mimo.hpp"
 #include "modem.hpp"
 #include "philox.hpp"
+#include "pilot_block.hpp"
 #include "pipe_common.hpp"
 #include "qam_pack.hpp"
 #include "totals.hpp"
@@ -37,21 +34,11 @@
 namespace mcle {
 
 constexpr int kPilotMax = 4;                                   // antennas per side
-constexpr int kPilotMaxPilots = 256;
 constexpr int kPilotSet = 2 * kPilotMax * kPilotMax;           // A [4][4] then G [4][4] of one filter
 constexpr int kPilotRec = 2 * kPilotSet + 1;                   // estimated CSI, perfect CSI, {ok, 0}
-// a Gram pivot at or below this share of the Gram matrix's trace counts as singular (host and device alike)
-constexpr double kPilotPivotFloor = 1e-12;
-
-struct PilotSetup {
-    int P, half;                                // half = ceil(P / 2)
-    int random_pilots, mmse_est, gram_ok;
-    double amp, sigma, alpha, filter_nv;        // sqrt(pilot_power), sqrt(noise_var)
-    double2 ginv[kPilotMax * kPilotMax];        // fixed pilots: (s s^H)^-1, entry [a][b] at a * kPilotMax + b
-};
 
 template <typename T, int NT, int NR>
-__global__ __launch_bounds__(64) void k_mimo_pilot_setup(PilotSetup p, const double2* __restrict__ pilots,
+__global__ __launch_bounds__(64) void k_mimo_pilot_setup(PilotSetup<kPilotMax> p, const double2* __restrict__ pilots,
                                                          const double2* __restrict__ Lm, const double2* __restrict__ Bm,
                                                          uint64_t seed, uint64_t first, uint64_t count,
                                                          cx<T>* __restrict__ recs, double* __restrict__ err_out,
@@ -140,50 +127,11 @@ __global__ __launch_bounds__(64) void k_mimo_pilot_setup(PilotSetup p, const dou
     bool ok = true;
     double inv_s2 = p.ginv[0].x;                 // nt = 1: 1 / |s|^2
     if (p.random_pilots) {
-        double tr = 0.0;
-#pragma unroll
-        for (int a = 0; a < NT; ++a) tr += Gm[a][a].x;
-        // Gram = C C^H, C lower triangular
-        double2 C[NT][NT];
         double invd[NT];
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-#pragma unroll
-            for (int i = j; i < NT; ++i) {
-                double2 a = Gm[i][j];
-#pragma unroll
-                for (int k = 0; k < j; ++k) a = csub(a, cmulc(C[i][k], C[j][k]));
-                if (i == j) {
-                    ok = ok && (a.x > kPilotPivotFloor * tr);
-                    C[j][j] = mk<double>(sqrt(a.x), 0.0);
-                    invd[j] = 1.0 / C[j][j].x;
-                } else {
-                    C[i][j] = cscale(a, invd[j]);
-                }
-            }
-        }
+        ok = pilot_gram_factor<NT>(Gm, invd);
         inv_s2 = invd[0] * invd[0];
-        // a row x of H^ solves x C C^H = R[r]: y C^H = R[r] forwards, x C = y backwards
 #pragma unroll
-        for (int r = 0; r < NR; ++r) {
-            double2 y[NT];
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                double2 v = R[r][j];
-#pragma unroll
-                for (int k = 0; k < j; ++k) v = csub(v, cmulc(y[k], C[j][k]));
-                y[j] = cscale(v, invd[j]);
-            }
-#pragma unroll
-            for (int j = NT - 1; j >= 0; --j) {
-                double2 v = y[j];
-#pragma unroll
-                for (int k = j + 1; k < NT; ++k) v = csub(v, cmul(y[k], C[k][j]));
-                y[j] = cscale(v, invd[j]);
-            }
-#pragma unroll
-            for (int a = 0; a < NT; ++a) Hest[r][a] = y[a];
-        }
+        for (int r = 0; r < NR; ++r) pilot_row_solve<NT>(Gm, invd, R[r], Hest[r]);
     } else {
         ok = p.gram_ok != 0;
 #pragma unroll
@@ -376,51 +324,8 @@ __global__ __launch_bounds__(256, pilot_walk_waves<T>()) void k_mimo_pilot_link(
     wg_flush_waves<4>(totals_all[1], counters ? counters + 1 : nullptr, n_sym, n_sym * mp.bits);
 }
 
-typedef std::complex<double> pilot_zc;
-
-// (s s^H)^-1 of the fixed pilots s [nt][P] by Gauss-Jordan with partial pivoting, complex128; false: numerically singular
-static bool pilot_gram_inverse(const pilot_zc* s, int nt, int P, double2* ginv) {
-    pilot_zc g[kPilotMax][kPilotMax], inv[kPilotMax][kPilotMax];
-    double tr = 0.0;
-    for (int a = 0; a < nt; ++a)
-        for (int b = 0; b < nt; ++b) {
-            pilot_zc acc(0.0, 0.0);
-            for (int p = 0; p < P; ++p) acc += s[a * P + p] * std::conj(s[b * P + p]);
-            g[a][b] = acc;
-            inv[a][b] = a == b ? pilot_zc(1.0, 0.0) : pilot_zc(0.0, 0.0);
-            if (a == b) tr += acc.real();
-        }
-    if (!std::isfinite(tr) || !(tr > 0.0)) return false;
-    for (int k = 0; k < nt; ++k) {
-        int piv = k;
-        for (int i = k + 1; i < nt; ++i)
-            if (std::abs(g[i][k]) > std::abs(g[piv][k])) piv = i;
-        if (!(std::abs(g[piv][k]) > kPilotPivotFloor * tr)) return false;
-        for (int j = 0; j < nt; ++j) {
-            std::swap(g[k][j], g[piv][j]);
-            std::swap(inv[k][j], inv[piv][j]);
-        }
-        const pilot_zc d = 1.0 / g[k][k];
-        for (int j = 0; j < nt; ++j) {
-            g[k][j] *= d;
-            inv[k][j] *= d;
-        }
-        for (int i = 0; i < nt; ++i) {
-            if (i == k) continue;
-            const pilot_zc f = g[i][k];
-            for (int j = 0; j < nt; ++j) {
-                g[i][j] -= f * g[k][j];
-                inv[i][j] -= f * inv[k][j];
-            }
-        }
-    }
-    for (int a = 0; a < nt; ++a)
-        for (int b = 0; b < nt; ++b) ginv[a * kPilotMax + b] = make_double2(inv[a][b].real(), inv[a][b].imag());
-    return true;
-}
-
 template <typename T, int NT, int NR>
-static void launch_pilot_setup(mcle_ctx* ctx, const PilotSetup& p, const double* d_pilots, const double* d_L, const double* d_B,
+static void launch_pilot_setup(mcle_ctx* ctx, const PilotSetup<kPilotMax>& p, const double* d_pilots, const double* d_L, const double* d_B,
                                uint64_t seed, uint64_t first, uint64_t m, void* recs, double* d_err, double* d_pow) {
     hipLaunchKernelGGL((k_mimo_pilot_setup<T, NT, NR>), dim3((unsigned)((m + 63) / 64)), dim3(64), 0, ctx->stream, p,
                        (const double2*)d_pilots, (const double2*)d_L, (const double2*)d_B, seed, first, m, (cx<T>*)recs, d_err,
@@ -428,7 +333,7 @@ static void launch_pilot_setup(mcle_ctx* ctx, const PilotSetup& p, const double*
 }
 
 template <typename T>
-static int run_mimo_pilot_link(mcle_ctx* ctx, const mcle_mimo_pilot_cfg* cfg, const PilotSetup& p, uint64_t seed, uint64_t first,
+static int run_mimo_pilot_link(mcle_ctx* ctx, const mcle_mimo_pilot_cfg* cfg, const PilotSetup<kPilotMax>& p, uint64_t seed, uint64_t first,
                                uint64_t count, const double* d_pilots, const double* d_L, const double* d_B,
                                mcle_counters* d_counters, uint32_t* d_sym_err, uint32_t* d_bit_err, double* d_err,
                                double* d_pow) {
@@ -476,36 +381,13 @@ extern "C" int mcle_run_mimo_pilot_link(mcle_ctx* ctx, int dtype, const mcle_mim
     if (ctx) ctx->last_kernel[0] = 0;
     int rc = check_pipe(ctx, dtype, cfg ? cfg->demod_method : 0, cfg);
     if (rc) return rc;
-    const int nt = cfg->nt, nr = cfg->nr, P = cfg->n_pilots;
+    const int nt = cfg->nt, nr = cfg->nr;
     MCLE_REQUIRE(nt >= 1 && nt <= nr && nr <= kPilotMax, "antenna counts must satisfy 1 <= nt <= nr <= %d (got nt %d, nr %d)", kPilotMax,
                  nt, nr);
-    MCLE_REQUIRE(P >= nt && P <= kPilotMaxPilots, "n_pilots must be in [nt, %d] (got %d pilots, nt %d)", kPilotMaxPilots, P, nt);
-    MCLE_REQUIRE(cfg->n_symbols >= 1, "n_symbols must be positive");
-    MCLE_REQUIRE(cfg->estimator == 0 || cfg->estimator == 1, "estimator must be 0 (LS) or 1 (MMSE) (got %d)", cfg->estimator);
-    MCLE_REQUIRE(cfg->random_pilots == 0 || cfg->random_pilots == 1, "random_pilots must be 0 or 1 (got %d)", cfg->random_pilots);
-    MCLE_REQUIRE(cfg->mmse_filter == 0 || cfg->mmse_filter == 1, "mmse_filter must be 0 or 1 (got %d)", cfg->mmse_filter);
-    MCLE_REQUIRE(std::isfinite(cfg->noise_var) && cfg->noise_var >= 0.0, "Noise variance must be a non-negative value.");
-    MCLE_REQUIRE(std::isfinite(cfg->pilot_power) && cfg->pilot_power > 0.0, "pilot_power must be finite and positive");
-    MCLE_REQUIRE(std::isfinite(cfg->alpha), "alpha must be finite");
-    MCLE_REQUIRE(cfg->random_pilots || d_pilots != nullptr, "null d_pilots with random_pilots = 0");
-    MCLE_REQUIRE(cfg->estimator == 0 || nt == 1, "the MMSE estimator needs nt = 1 (got %d)", nt);
-    MCLE_REQUIRE(cfg->estimator == 0 || d_mmse_matrix != nullptr, "the MMSE estimator needs d_mmse_matrix (from a covariance)");
-    if ((rc = check_link_draws((uint64_t)nr, cfg->n_symbols, count))) return rc;
+    if ((rc = check_pilot_cfg(cfg, d_pilots, d_mmse_matrix, count))) return rc;
     if (count == 0) return MCLE_OK;
-    MCLE_REQUIRE(d_counters != nullptr, "null d_counters");
-    if ((rc = ctx->bind())) return rc;
-    PilotSetup p{};
-    p.P = P, p.half = (P + 1) / 2;
-    p.random_pilots = cfg->random_pilots, p.mmse_est = cfg->estimator, p.gram_ok = 1;
-    p.amp = std::sqrt(cfg->pilot_power), p.sigma = std::sqrt(cfg->noise_var), p.alpha = cfg->alpha;
-    p.filter_nv = cfg->mmse_filter ? cfg->noise_var : 0.0;
-    if (!cfg->random_pilots) {
-        // the fixed block's inverse Gram matrix, once, on the host
-        std::vector<pilot_zc> s((size_t)nt * P);
-        MCLE_HIP(hipMemcpyAsync(s.data(), d_pilots, s.size() * sizeof(pilot_zc), hipMemcpyDeviceToHost, ctx->stream));
-        MCLE_HIP(hipStreamSynchronize(ctx->stream));
-        p.gram_ok = pilot_gram_inverse(s.data(), nt, P, p.ginv) ? 1 : 0;
-    }
+    PilotSetup<kPilotMax> p;
+    if ((rc = pilot_setup_fill(ctx, cfg, d_pilots, d_counters, p))) return rc;
     return dtype == MCLE_F32 ? run_mimo_pilot_link<float>(ctx, cfg, p, seed, first, count, d_pilots, d_chan_factor, d_mmse_matrix,
                                                           d_counters, d_sym_err, d_bit_err, d_err, d_pow)
                              : run_mimo_pilot_link<double>(ctx, cfg, p, seed, first, count, d_pilots, d_chan_factor, d_mmse_matrix,

@@ -6,6 +6,8 @@ A/B of two builds of the library: run once per build with MCLE_LIBRARY pointing 
                        min-distance; both arithmetics (scripts/bench_mimo_schemes.py)
     k_mimo_pilot_link  4 x 4, P = 16, 2^20 realizations, slicer (scripts/bench_pilot_link.py)
     k_mimo_large_link  8 x 8, 2^20 realizations, slicer (scripts/bench_mimo_large.py)
+    k_mimo_large_pilot_link  8 x 8 with P = 16 in both arithmetics and 8 x 16 with P = 64 in complex128 (dominated by the set-up
+                       kernel), LS estimate from drawn pilots, 2^20 realizations, slicer (scripts/bench_large_pilot.py)
     k_comp_link        variant None, 3 cells of 2 x 2, one interferer antenna, NSymbs 500, 4-PSK (scripts/bench_comp.py)
     k_iagl_link        K = 3, 5 x 3, Ns = 2, max-SINR with max_iterations = 1 (the fewest the entry point accepts), 2^16 realizations
     k_ia_link          bench.py's c5: 262 144 realizations of 200 columns, 16-QAM, 20 dB, slicer, walk_legacy = 1
@@ -91,6 +93,10 @@ for dtype in ("f32", "f64"):
             lambda first: eng.run_mimo_pilot_link(4, 4, 16, 200, NV15, 1, first, n, method=_lib.DEMOD_QAM_SLICER, dtype=dtype))
     measure("large 8x8 %s" % dtype,
             lambda first: eng.run_mimo_large(8, 8, 200, NV15, 1, first, n, method=_lib.DEMOD_QAM_SLICER, dtype=dtype))
+    measure("large pilot 8x8 P16 %s" % dtype,
+            lambda first: eng.run_mimo_large_pilot_link(8, 8, 16, 200, NV15, 1, first, n, method=_lib.DEMOD_QAM_SLICER, dtype=dtype))
+measure("large pilot 8x16 P64 f64",          # the set-up kernel's share is largest here: 64 pilots through 16 receive rows
+        lambda first: eng.run_mimo_large_pilot_link(8, 16, 64, 200, NV15, 1, first, n, method=_lib.DEMOD_QAM_SLICER, dtype="f64"))
 n = max((1 << 16) // scale, 64)
 for dtype in ("f32", "f64"):
     measure("iagl K3 5x3 Ns2 it1 %s" % dtype,
