@@ -1241,6 +1241,74 @@ int mcle_run_indoor_drops(mcle_ctx* ctx, int dtype, const mcle_indoor_cfg* cfg, 
                           double* d_sum_sinr_dB, double* d_min_sinr_dB, int32_t* d_active_aps, double* d_sinr_dB,
                           double* d_capacity, int32_t* d_assoc);
 
+/* ---- hexagonal-cell system level: a cluster of hexagonal cells (apps/comp_BD/simulate_comp.py 'Random' users; cell/cell.py) -
+ * num_cells (K, 1 .. 19) hexagonal cells of cell_radius with a base station in every centre.  The geometry is the HOST's
+ * (pyphysim_amd/cell.py restates cell.Cluster): the config carries, per cell c, the positions pos_x / pos_y [pos_start[c] ..
+ * pos_start[c + 1]) -- the cell's centre first, then with wrap_around (19 cells only) its two or three wrapped copies --, the
+ * cluster centre and the cluster's external radius.  Positions, offsets and squared distances are f64 in either arithmetic; from
+ * the logarithm of the squared distance on everything is `dtype`.
+ *     distance d[p][c] = |p - centre_c|, with wrap_around the minimum over the cell's positions;
+ *     gain g[p][c] = 10^(-PL_dB(d) / 10):  MCLE_HEX_PL_NONE 1;  MCLE_HEX_PL_GENERAL 10 n log10(d dist_scale) + C dB
+ *         (PathLoss3GPP1 on km: 3.76, 128.1, 1; PathLossFreeSpace).  SMALL DISTANCES: a negative loss in dB is clamped to 0 dB,
+ *         gain 1, d = 0 included -- the reference's handle_small_distances_bool = True; with it off the reference raises below
+ *         3.9e-4 km for 3GPP1, which a Monte Carlo over 1e6 drops meets about once;
+ *     interferer gain g_ext[p] = the model at external_radius - |p - cluster centre| under the same clamp (app :205-213); a
+ *         point on or beyond the external circle is taken as ON the interferer (distance 0, gain 1);
+ *     SINR of a point served by cell c = tx g[p][c] / (sum_{c' != c} tx g[p][c'] + ext_power g_ext[p] + noise), the
+ *         interference summed directly, never as total minus desired.  n_ext only sets how often the records repeat g_ext.
+ *
+ * mcle_hex_gains: the operator on injected points.  d_points [n][2] (x, y) -> d_dist [n][K], d_gain [n][K + 1] (the last column
+ * is the interferer), d_sinr_dB [n] (served by d_assoc), d_assoc [n]: the FIRST cell of the largest gain.  Any output may be
+ * NULL; users_per_cell, min_dist_ratio and the histogram fields are ignored.
+ *
+ * mcle_run_hex_drops: Monte Carlo over user drops, one drop per wavefront.  Drop r (realization first + r of mcle-philox-v1)
+ * places users_per_cell (U) users in every cell, user q = cell U + slot; every user is served by the cell it was dropped in.
+ * Attempt t (0 <= t < 128) of user q takes the uniforms 2 (128 q + t) and 2 (128 q + t) + 1 of stream 5 (STREAM_DROP; the
+ * channel stream that mcle_run_comp reads on the same (seed, realization) is not touched): the candidate centre + (2 (u_x - 1/2)
+ * r, 2 (u_y - 1/2) r), every operation rounded on its own, wins if it is inside the cell (|y| < h and sqrt(3) |x| + |y| < 2 h on
+ * the offset, h = sqrt(3) r / 2) and at least min_dist_ratio r from the centre.  A user that exhausts its 128 attempts
+ * (probability below 1e-17) sets d_flags[r] = 1: the drop's floating outputs are NaN and it is left out of the histogram.
+ * With d_positions [count][K U][2] not NULL nothing is drawn.
+ *     d_flags [count] (int32); d_records [count][K U][K + n_ext]: the gains, the interferer's repeated n_ext times -- with U = 1
+ *     the d_pathloss of mcle_run_comp; d_pos_out [count][K U][2]; d_sinr_dB, d_capacity [count][K U] (capacity = log2(1 +
+ *     SINR), f64 from the dtype SINR); d_hist [hist_bins + 2]: users by SINR in dB as for mcle_run_indoor_drops, ACCUMULATED
+ *     into the caller's zeroed uint64 counters; d_sum_capacity, d_min_sinr_dB [count]: over the drop's users.
+ * Every output pointer may be NULL; outputs are double in either arithmetic.  Every output of a drop is a function of (seed,
+ * drop, cfg, dtype) alone: bit for bit independent of the grid, of MCLE_OPT_GRID_OVERSUB and of how [first, first + count) is
+ * split.
+ * Envelope: num_cells 1 .. 19, users_per_cell >= 1 with num_cells users_per_cell <= 256, min_dist_ratio in [0, 0.7],
+ * wrap_around 0 / 1 (1: 19 cells), n_ext 0 .. 8, hist_bins 0 .. 256 (hist_step_dB > 0 with bins), cell_radius > 0, GENERAL: pl_n
+ * > 0 and dist_scale > 0, tx_power > 0, noise_power > 0, ext_power >= 0 (in f32 normal f32 numbers, ext_power or 0), n_pos in
+ * [num_cells, 64] with pos_start from 0 to n_pos in steps of 1 (with wrap_around 1 .. 4), finite positions, external_radius > 0,
+ * n and count <= 2^31-1; anything else is MCLE_E_INVAL with a message that names the argument (the rules are checked before the
+ * context and the pointers).  n = 0 / count = 0 returns MCLE_OK and launches nothing.
+ * mcle_ctx_last_kernel: "hex_gains f64|f32 m<model> w<wrap>", "hex_drops f64|f32 m<model> u<users per lane: 1, 2 or 4>
+ * w<wrap>". */
+enum { MCLE_HEX_PL_NONE = 0, MCLE_HEX_PL_GENERAL = 1 };
+#define MCLE_HEX_MAX_POS 64
+typedef struct mcle_hex_cfg {
+    int32_t num_cells;        /* 1..19 */
+    int32_t users_per_cell;   /* drops only: num_cells * users_per_cell <= 256 */
+    int32_t model;            /* MCLE_HEX_PL_* */
+    int32_t wrap_around;      /* 0 / 1 (19 cells only) */
+    int32_t n_ext;            /* 0..8: copies of the interferer's column in the records */
+    int32_t hist_bins;        /* 0..256 */
+    int32_t n_pos;            /* entries of pos_x / pos_y */
+    int32_t reserved;
+    double cell_radius, min_dist_ratio;
+    double pl_n, pl_C, dist_scale;  /* GENERAL: 10 n log10(d * dist_scale) + C (3GPP on km: 3.76, 128.1, 1) */
+    double tx_power, noise_power, ext_power;   /* linear */
+    double hist_lo_dB, hist_step_dB;
+    double external_radius, centre_x, centre_y;
+    int32_t pos_start[20];
+    double pos_x[MCLE_HEX_MAX_POS], pos_y[MCLE_HEX_MAX_POS];
+} mcle_hex_cfg;
+int mcle_hex_gains(mcle_ctx* ctx, int dtype, const mcle_hex_cfg* cfg, const double* d_points, size_t n, double* d_dist,
+                   double* d_gain, double* d_sinr_dB, int32_t* d_assoc);
+int mcle_run_hex_drops(mcle_ctx* ctx, int dtype, const mcle_hex_cfg* cfg, uint64_t seed, uint64_t first, uint64_t count,
+                       const double* d_positions, int32_t* d_flags, double* d_records, double* d_pos_out, double* d_sinr_dB,
+                       double* d_capacity, uint64_t* d_hist, double* d_sum_capacity, double* d_min_sinr_dB);
+
 /* ---- same-seed parity mode: NumPy's legacy global RandomState replayed on the device -------
  * Realization r receives exactly what the reference draws after np.random.seed(seed_base + r)
  * (legacy MT19937; util/misc.py:327-355 randn_c = randn real block then imag block, and

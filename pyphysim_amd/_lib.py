@@ -199,6 +199,18 @@ INDOOR_MODELS = {"none": 0, "general": 1, "metis_ps7": 2}
 INDOOR_ASSOC = {"closest": 0, "best_channel": 1}
 
 
+class HexCfg(Structure):
+    _fields_ = [("num_cells", c_int32), ("users_per_cell", c_int32), ("model", c_int32), ("wrap_around", c_int32),
+                ("n_ext", c_int32), ("hist_bins", c_int32), ("n_pos", c_int32), ("reserved", c_int32),
+                ("cell_radius", c_double), ("min_dist_ratio", c_double), ("pl_n", c_double), ("pl_C", c_double),
+                ("dist_scale", c_double), ("tx_power", c_double), ("noise_power", c_double), ("ext_power", c_double),
+                ("hist_lo_dB", c_double), ("hist_step_dB", c_double), ("external_radius", c_double), ("centre_x", c_double),
+                ("centre_y", c_double), ("pos_start", c_int32 * 20), ("pos_x", c_double * 64), ("pos_y", c_double * 64)]
+
+
+HEX_MODELS = {"none": 0, "general": 1}
+
+
 class LegacySeg(Structure):
     _fields_ = [("kind", c_int32), ("n", c_int32), ("range", c_uint32), ("reserved", c_uint32)]
 
@@ -324,6 +336,8 @@ _PROTOS = {
     "mcle_indoor_sinr": (c_int, [_P, c_int, POINTER(IndoorCfg), _P, c_size_t, _P, _P]),
     "mcle_run_indoor_drops": (c_int, [_P, c_int, POINTER(IndoorCfg), c_uint64, c_uint64, c_uint64, _P, _P, _P, _P, _P, _P, _P, _P,
                                       _P, _P]),
+    "mcle_hex_gains": (c_int, [_P, c_int, POINTER(HexCfg), _P, c_size_t, _P, _P, _P, _P]),
+    "mcle_run_hex_drops": (c_int, [_P, c_int, POINTER(HexCfg), c_uint64, c_uint64, c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mcle_legacy_draws": (c_int, [_P, POINTER(LegacySeg), c_int, c_uint32, c_uint64, c_uint64, _P, c_size_t, _P,
                                   c_size_t, _P]),
     "mcle_complex_from_parts": (c_int, [_P, c_int, _P, _P, c_double, _P, c_size_t]),

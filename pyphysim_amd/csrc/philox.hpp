@@ -18,7 +18,7 @@
 
 namespace mcle {
 
-enum : uint32_t { STREAM_DATA = 0, STREAM_NOISE = 1, STREAM_CHAN = 2, STREAM_PHASE = 3, STREAM_PILOT = 4 };
+enum : uint32_t { STREAM_DATA = 0, STREAM_NOISE = 1, STREAM_CHAN = 2, STREAM_PHASE = 3, STREAM_PILOT = 4, STREAM_DROP = 5 };
 
 struct Words4 {
     uint32_t w[4];

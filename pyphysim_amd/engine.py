@@ -1083,6 +1083,100 @@ class Engine:
             res.update(sinr_dB=per[0].get(), capacity=per[1].get(), assoc=per[2].get())
         return res
 
+    # ---- hexagonal-cell system level (mcle_hex_gains / mcle_run_hex_drops; csrc/pipeline_hex.hip) ----
+    @staticmethod
+    def _hex_cfg(num_cells, cell_radius, users_per_cell=1, model="general", wrap_around=False, n_ext=0, min_dist_ratio=0.0,
+                 pl_n=3.76, pl_C=128.1, dist_scale=1.0, tx_power=1.0, noise_power=1e-13, ext_power=0.0, hist_bins=0,
+                 hist_lo_dB=0.0, hist_step_dB=1.0):
+        """The config with the geometry tables of pyphysim_amd.cell; a cluster the host geometry refuses is left to the
+        library's own message (its tables stay empty)."""
+        from . import cell
+        cfg = _lib.HexCfg()
+        cfg.num_cells, cfg.users_per_cell, cfg.model = int(num_cells), int(users_per_cell), int(_lib.HEX_MODELS.get(model, model))
+        cfg.wrap_around, cfg.n_ext, cfg.hist_bins = int(bool(wrap_around)), int(n_ext), int(hist_bins)
+        cfg.cell_radius, cfg.min_dist_ratio = float(cell_radius), float(min_dist_ratio)
+        cfg.pl_n, cfg.pl_C, cfg.dist_scale = float(pl_n), float(pl_C), float(dist_scale)
+        cfg.tx_power, cfg.noise_power, cfg.ext_power = float(tx_power), float(noise_power), float(ext_power)
+        cfg.hist_lo_dB, cfg.hist_step_dB = float(hist_lo_dB), float(hist_step_dB)
+        K, r = int(num_cells), float(cell_radius)
+        if 1 <= K <= cell.MAX_CELLS and np.isfinite(r) and r > 0 and (not wrap_around or K == 19):
+            pos, start, ext_radius, centre = cell.hex_tables(K, r, bool(wrap_around))
+            cfg.n_pos, cfg.external_radius = len(pos), float(ext_radius)
+            cfg.centre_x, cfg.centre_y = float(centre.real), float(centre.imag)
+            for i, v in enumerate(start):
+                cfg.pos_start[i] = int(v)
+            for i, v in enumerate(pos):
+                cfg.pos_x[i], cfg.pos_y[i] = float(v.real), float(v.imag)
+        return cfg
+
+    @staticmethod
+    def _points_xy(points, what="points"):
+        pts = np.asarray(points)
+        if np.iscomplexobj(pts):
+            return pts.shape, np.ascontiguousarray(pts, dtype=np.complex128).reshape(-1).view(np.float64)
+        if pts.ndim < 1 or pts.shape[-1] != 2:
+            raise ValueError("%s must be complex or real [..., 2] (got %s)" % (what, pts.shape))
+        return pts.shape[:-1], np.ascontiguousarray(pts, dtype=np.float64).reshape(-1)
+
+    def hex_gains(self, points, num_cells, cell_radius, dtype=None, **cfg):
+        """Distances, gains, SINR and best cell of every point against a cluster of `num_cells` hexagonal cells
+        (mcle_hex_gains; pyphysim_amd.cell.Cluster's geometry).  points: complex (x + 1j y) of any shape, or real [..., 2].
+        Keywords: model 'none' / 'general' (10 pl_n log10(d dist_scale) + pl_C dB; default PathLoss3GPP1 on km),
+        wrap_around (19 cells), tx_power, noise_power, ext_power (linear).  Returns a dict: 'dist' [..., K], 'gain'
+        [..., K + 1] (last column: the interferer), 'sinr_dB' [...], 'assoc' [...] (first cell of the largest gain)."""
+        dt = self._dt(dtype)
+        shape, xy = self._points_xy(points)
+        n, K = xy.size // 2, max(int(num_cells), 0)
+        c = self._hex_cfg(num_cells, cell_radius, **cfg)
+        d_xy = self.to_device(xy)
+        dist, gain = self.empty((n, K), np.float64), self.empty((n, K + 1), np.float64)
+        sinr, idx = self.empty(n, np.float64), self.empty(n, np.int32)
+        self._raise_value(self.lib.mcle_hex_gains(self.ctx, dt, byref(c), d_xy.ptr, n, dist.ptr, gain.ptr, sinr.ptr, idx.ptr))
+        return dict(dist=dist.get().reshape(shape + (K,)), gain=gain.get().reshape(shape + (K + 1,)),
+                    sinr_dB=sinr.get().reshape(shape), assoc=idx.get().reshape(shape))
+
+    def run_hex_drops(self, num_cells, cell_radius, users_per_cell, seed, first, count, positions=None, dtype=None,
+                      per_user=False, records=False, **cfg):
+        """`count` user drops in a cluster of hexagonal cells (mcle_run_hex_drops; the 'Random' user positioning of
+        apps/comp_BD/simulate_comp.py): drop r places users_per_cell users at random in every cell from the Philox draws of
+        realization first + r (or at positions [count, K U], complex or real [..., 2], host or resident float64
+        [count, K U, 2]); every user is served by its own cell.  Keywords as for hex_gains plus min_dist_ratio, n_ext,
+        hist_bins, hist_lo_dB, hist_step_dB.  Returns a dict: 'flags' [count], 'hist' [hist_bins + 2] (exact counts),
+        'sum_capacity', 'min_sinr_dB' [count]; with per_user also 'positions' (complex), 'sinr_dB', 'capacity' [count, K U];
+        with records=True also 'records': the RESIDENT float64 [count, K U, K + n_ext] of linear path losses -- with one user
+        per cell what run_comp takes as pathloss_per_realization."""
+        dt = self._dt(dtype)
+        count, K, U = int(count), max(int(num_cells), 0), max(int(users_per_cell), 0)
+        KU, E = K * U, max(int(cfg.get("n_ext", 0)), 0)
+        c = self._hex_cfg(num_cells, cell_radius, users_per_cell, **cfg)
+        d_pos = None
+        if isinstance(positions, DeviceArray):
+            if positions.dtype != np.dtype(np.float64) or positions.size != count * KU * 2:
+                raise ValueError("device positions must be float64 [count, K U, 2]")
+            d_pos = positions
+        elif positions is not None:
+            _, pos = self._points_xy(positions, "positions")
+            if pos.size != count * KU * 2:
+                raise ValueError("positions must hold count x K U points (got %d values)" % (pos.size // 2))
+            d_pos = self.to_device(pos)
+        hist = self.zeros(max(int(cfg.get("hist_bins", 0)), 0) + 2, np.uint64)
+        flags = self.empty(count, np.int32)
+        per_drop = [self.empty(count, np.float64) for _ in range(2)]
+        rec = self.empty((count, KU, K + E), np.float64) if records else None
+        per = ([self.empty((count, KU, 2), np.float64)] + [self.empty((count, KU), np.float64) for _ in range(2)]
+               if per_user else [None] * 3)
+        ptr = lambda a: a.ptr if a is not None else None
+        self._raise_value(self.lib.mcle_run_hex_drops(self.ctx, dt, byref(c), int(seed), int(first), count, ptr(d_pos),
+                                                      flags.ptr, ptr(rec), ptr(per[0]), ptr(per[1]), ptr(per[2]), hist.ptr,
+                                                      per_drop[0].ptr, per_drop[1].ptr))
+        res = dict(flags=flags.get(), hist=hist.get(), sum_capacity=per_drop[0].get(), min_sinr_dB=per_drop[1].get())
+        if per_user:
+            res.update(positions=np.ascontiguousarray(per[0].get()).view(np.complex128).reshape(count, KU),
+                       sinr_dB=per[1].get(), capacity=per[2].get())
+        if records:
+            res["records"] = rec
+        return res
+
     def ia_iterative(self, solver, big_H, F_init, noise_var, max_iterations=50, relative_factor=1e-6,
                      initialize_with="fix"):
         """IterativeIASolverBaseClass.solve (algorithms.py:802-883) with initialize_with='fix': big_H

@@ -2,7 +2,7 @@
 PathLoss3GPP1, :1022-1342 PathLossMetisPS7): what the CoMP application's power rule needs (apps/comp_BD/simulate_comp.py:629-659
 -- the loss at the cell border fixes the transmit power for a wanted SNR there) and what the indoor scenario of
 apps/metis_scenarios/ evaluates per (user, access point) pair (pyphysim_amd/metis.py; on the GPU csrc/pipeline_indoor.hip).
-Cell geometry is out of scope: the distances come from the user.
+The distances come from the user, or from the hexagonal cluster of pyphysim_amd/cell.py (on the GPU csrc/pipeline_hex.hip).
 
     >>> pl = PathLoss3GPP1()
     >>> pl.calc_path_loss(1)

@@ -701,7 +701,14 @@ class CompSimulator(BatchedSimulationRunner):
     whose loss is `path_loss_border` (default: PathLoss3GPP1 at 1 km when a path loss is given, else 1).
 
     `pathloss` [K, K] (rx user, tx cell) and `pathloss_ext` [K, ext_int_rank]: arrays, or `pathloss` a callable
-    (first, count) -> [count, K, K + ext_int_rank] for per-drop scenarios (cell geometry itself is out of scope).
+    (first, count) -> [count, K, K + ext_int_rank] for per-drop scenarios of the user's own.
+
+    `user_positioning_method` (the app's parameter; not together with `pathloss`) takes the path loss from the hexagonal
+    cluster of `K` cells of `cell_radius` km instead (pyphysim_amd.cell, PathLoss3GPP1 with the small-distance clamp, the
+    interferer at external_radius - distance to the cluster centre): 'Random' drops one user per cell anew in EVERY
+    repetition -- one Engine.run_hex_drops per batch on the variation's seed, whose resident records every variant's
+    run_comp reads, no host round trip; 'Symmetric Far Away' (K = 3) places the users once at 70 % of the way to the far
+    vertex of each cell and runs the fixed-matrix path.  `path_loss_border` then defaults to the model at `cell_radius`.
 
     Results per variant v, formed per realization and per stream as simulate_comp.py:556-621 does: 'ber_v', 'ser_v',
     'per_v' (per = 1 - (1 - ber_stream)^packet_length, errors = per x packages, summed over the streams), 'spec_effic_v'
@@ -714,9 +721,21 @@ class CompSimulator(BatchedSimulationRunner):
     def __init__(self, SNR, Pe_dBm, modulator="psk", M=4, K=3, Nr=2, ext_int_rank=1, NSymbs=500, packet_length=60,
                  N0_dBm=-116.4, variants=VARIANTS, num_streams=1, pathloss=None, pathloss_ext=None, path_loss_border=None,
                  rep_max=1000, seed=0, batch_size=4096, dtype="f64", demod="auto", engine=None,
-                 common_random_numbers=False, process_group=None):
+                 common_random_numbers=False, process_group=None, user_positioning_method=None, cell_radius=1.0):
         super().__init__(batch_size=batch_size, process_group=process_group)
         from .pathloss import PathLoss3GPP1
+        if user_positioning_method not in (None, "Random", "Symmetric Far Away"):
+            raise ValueError("user_positioning_method must be None, 'Random' or 'Symmetric Far Away' (got %r)"
+                             % (user_positioning_method,))
+        if user_positioning_method is not None:
+            if pathloss is not None or pathloss_ext is not None:
+                raise ValueError("give user_positioning_method or pathloss, not both")
+            if not (np.isfinite(cell_radius) and cell_radius > 0):
+                raise ValueError("cell_radius must be positive (got %r)" % (cell_radius,))
+            if user_positioning_method == "Symmetric Far Away" and int(K) != 3:
+                raise ValueError("'Symmetric Far Away' needs K = 3 (got %d)" % int(K))
+        self.user_positioning_method = user_positioning_method
+        self.cell_radius = float(cell_radius)
         self.rep_max = rep_max
         self.seed = int(seed)
         self.dtype = dtype
@@ -737,8 +756,13 @@ class CompSimulator(BatchedSimulationRunner):
             self._ple = np.zeros((int(K), 0)) if pathloss_ext is None else np.asarray(pathloss_ext, dtype=float)
             if self._pl.shape != (int(K), int(K)) or self._ple.shape != (int(K), int(ext_int_rank)):
                 raise ValueError("pathloss must be [K, K] and pathloss_ext [K, ext_int_rank]")
+        if user_positioning_method == "Symmetric Far Away":
+            self._pl, self._ple = self.far_away_pathloss(self.cell_radius, int(ext_int_rank))
         if path_loss_border is None:
-            path_loss_border = 1.0 if pathloss is None else PathLoss3GPP1().calc_path_loss(1.0)
+            if user_positioning_method is not None:
+                path_loss_border = PathLoss3GPP1().calc_path_loss(self.cell_radius)
+            else:
+                path_loss_border = 1.0 if pathloss is None else PathLoss3GPP1().calc_path_loss(1.0)
         self.path_loss_border = float(path_loss_border)
         keys = []
         for v in self.variants:
@@ -758,6 +782,31 @@ class CompSimulator(BatchedSimulationRunner):
     _seed_for = _LinkSimulator._seed_for
     _bind = _LinkSimulator._bind
 
+    @staticmethod
+    def far_away_pathloss(cell_radius=1.0, ext_int_rank=1):
+        """(pathloss [3, 3], pathloss_ext [3, ext_int_rank]) of the app's 'Symmetric Far Away' users (:172-213)."""
+        from .cell import Cluster
+        from .pathloss import PathLoss3GPP1
+        cluster = Cluster(cell_radius, 3)
+        cluster.add_border_users([1, 2, 3], [210, -30, 90], 0.7)
+        model = PathLoss3GPP1()
+        model.handle_small_distances_bool = True
+        to_centre = np.array([cluster.calc_dist(u) for u in cluster.get_all_users()])
+        ext = model.calc_path_loss(cluster.external_radius - to_centre)
+        return (model.calc_path_loss(cluster.calc_dist_all_users_to_each_cell()),
+                np.repeat(ext[:, np.newaxis], int(ext_int_rank), axis=1))
+
+    def drop_records(self, eng, current_parameters, first_rep, count):
+        """The resident path-loss records [count, K, K + ext_int_rank] of the 'Random' users of repetitions [first_rep,
+        first_rep + count) of this variation."""
+        p = current_parameters
+        out = eng.run_hex_drops(p["K"], self.cell_radius, 1, self._seed_for(p), first_rep, count, n_ext=p["ext_int_rank"],
+                                dtype=self.dtype, records=True)
+        if out["flags"].any():
+            raise RuntimeError("a user drop ran out of placement attempts (repetition %d)"
+                               % (int(first_rep) + int(np.flatnonzero(out["flags"])[0])))
+        return out["records"]
+
     def _run_batch(self, current_parameters, first_rep, count):
         from .pathloss import transmit_power_for_border_loss
         p = current_parameters
@@ -770,6 +819,8 @@ class CompSimulator(BatchedSimulationRunner):
         per_drop = None
         if self._pl_call is not None and count:
             per_drop = eng.to_device(np.ascontiguousarray(self._pl_call(int(first_rep), int(count)), dtype=np.float64))
+        elif self.user_positioning_method == "Random" and count:
+            per_drop = self.drop_records(eng, p, first_rep, count)
         c = None
         slot = np.arange(K * r) % r
         for v in self.variants:
@@ -900,6 +951,93 @@ class MetisDropSimulator(BatchedSimulationRunner):
         res.add_result(Result.from_batch("sum_capacity", Result.RATIOTYPE, cap, n, cap, cap_sq, n))
         act, act_sq = int(round(gf("active_aps_sum"))), int(round(gf("active_aps_sq")))
         res.add_result(Result.from_batch("active_aps", Result.RATIOTYPE, act, n, float(act), float(act_sq), n))
+        hist = [int(round(gf("sinr_h%d" % i))) for i in range(self.hist_bins + 2)]
+        res.add_result(Result.from_histogram("sinr_histogram", hist))
+        return res
+
+
+class HexDropSimulator(BatchedSimulationRunner):
+    """Monte Carlo over user drops in a cluster of hexagonal cells -- the system-level experiment the reference's cell.Cluster
+    exists for: `num_cells` (1 .. 19) cells of `cell_radius` km, `users_per_cell` users dropped uniformly in every cell at
+    least `min_dist_ratio` radii from its base station, each served by its own cell while every other cell interferes;
+    PathLoss3GPP1 with the small-distance clamp; optionally an external interferer of `ext_power_dBm` at the cluster's
+    external radius and wrap around (19 cells).  A repetition is a drop; one Engine.run_hex_drops per batch.  Any of the
+    scalars may be a list: every combination is one parameter variation.
+
+    Results: 'sinr_dB' and 'capacity' (RATIO against users: the mean per user), 'sum_capacity' and 'min_sinr_dB' (RATIO
+    against drops), 'sinr_histogram' (CHOICE over hist_bins + 2 slots of width hist_step_dB from hist_lo_dB: below, the bins,
+    at or above the top).  Sums and the histogram travel through EXTRA_KEYS, so sharding and partial-result resume keep
+    them.  A drop the device flags (a user out of placement attempts: probability below 1e-17 per user) is left out."""
+
+    _SUMS = ("users", "drops", "sinr_dB_sum", "sinr_dB_sq", "capacity_sum", "capacity_sq", "min_sinr_dB_sum", "min_sinr_dB_sq")
+    _SCALARS = ("num_cells", "cell_radius", "users_per_cell", "Pt_dBm", "noise_power_dBm", "min_dist_ratio", "ext_power_dBm")
+
+    def __init__(self, num_cells=19, cell_radius=1.0, users_per_cell=10, Pt_dBm=46.0, noise_power_dBm=-104.0,
+                 min_dist_ratio=0.0, ext_power_dBm=None, wrap_around=False, rep_max=1000, hist_bins=60, hist_lo_dB=-10.0,
+                 hist_step_dB=1.0, seed=0, batch_size=4096, dtype="f32", engine=None, common_random_numbers=False,
+                 process_group=None):
+        super().__init__(batch_size=batch_size, process_group=process_group)
+        self.rep_max = rep_max
+        self.seed = int(seed)
+        self.dtype = dtype
+        self.common_random_numbers = common_random_numbers
+        self._engine = engine
+        self.wrap_around = bool(wrap_around)
+        self.hist_bins, self.hist_lo_dB, self.hist_step_dB = int(hist_bins), float(hist_lo_dB), float(hist_step_dB)
+        self.EXTRA_KEYS = self._SUMS + tuple("sinr_h%d" % i for i in range(self.hist_bins + 2))
+        self.EXTRA_INT_KEYS = ("users", "drops") + self.EXTRA_KEYS[len(self._SUMS):]
+        values = dict(zip(self._SCALARS, (num_cells, cell_radius, users_per_cell, Pt_dBm, noise_power_dBm, min_dist_ratio,
+                                          -np.inf if ext_power_dBm is None else ext_power_dBm)))
+        for k, v in values.items():
+            if np.ndim(v) > 0:
+                self.params.add(k, np.asarray(v))
+                self.params.set_unpack_parameter(k)
+            else:
+                self.params.add(k, v)
+
+    engine = _LinkSimulator.engine
+    _seed_for = _LinkSimulator._seed_for
+
+    def drop_args(self, current_parameters):
+        """The variation as keyword arguments of Engine.run_hex_drops."""
+        from .util import dBm2Linear
+        p = current_parameters
+        pe = float(p["ext_power_dBm"])
+        return dict(num_cells=int(p["num_cells"]), cell_radius=float(p["cell_radius"]), users_per_cell=int(p["users_per_cell"]),
+                    model="general", wrap_around=self.wrap_around, min_dist_ratio=float(p["min_dist_ratio"]),
+                    tx_power=float(dBm2Linear(p["Pt_dBm"])), noise_power=float(dBm2Linear(p["noise_power_dBm"])),
+                    ext_power=float(dBm2Linear(pe)) if np.isfinite(pe) else 0.0, hist_bins=self.hist_bins,
+                    hist_lo_dB=self.hist_lo_dB, hist_step_dB=self.hist_step_dB, dtype=self.dtype)
+
+    def _run_batch(self, current_parameters, first_rep, count):
+        out = self.engine.run_hex_drops(seed=self._seed_for(current_parameters), first=first_rep, count=count, per_user=True,
+                                        **self.drop_args(current_parameters))
+        c = {k: 0 for k in self.COUNTER_KEYS + ("n_symbols", "n_bits")}
+        c["n_realizations"] = int(count)
+        KU = int(current_parameters["num_cells"]) * int(current_parameters["users_per_cell"])
+        ok = out["flags"] == 0
+        mean_db = out["sinr_dB"][ok].sum(axis=1) / KU                               # one RATIO update per drop
+        cap, low = out["sum_capacity"][ok], out["min_sinr_dB"][ok]
+        c.update(users=int(ok.sum()) * KU, drops=int(ok.sum()), sinr_dB_sum=float(mean_db.sum()),
+                 sinr_dB_sq=float(np.square(mean_db).sum()), capacity_sum=float(cap.sum()), capacity_sq=float(np.square(cap).sum()),
+                 min_sinr_dB_sum=float(low.sum()), min_sinr_dB_sq=float(np.square(low).sum()))
+        for i, h in enumerate(out["hist"].tolist()):
+            c["sinr_h%d" % i] = int(h)
+        return c
+
+    def _results_from_counters(self, current_parameters, c):
+        from .simulations import Result, SimulationResults
+        res = SimulationResults()
+        gf = lambda k: float(c.get(k, 0.0))
+        users, n = int(round(gf("users"))), int(round(gf("drops")))
+        KU = int(current_parameters["num_cells"]) * int(current_parameters["users_per_cell"])
+        cap, cap_sq = gf("capacity_sum"), gf("capacity_sq")
+        res.add_result(Result.from_batch("sinr_dB", Result.RATIOTYPE, gf("sinr_dB_sum") * KU, users, gf("sinr_dB_sum"),
+                                         gf("sinr_dB_sq"), n))
+        res.add_result(Result.from_batch("capacity", Result.RATIOTYPE, cap, users, cap / KU, cap_sq / (KU * KU), n))
+        res.add_result(Result.from_batch("sum_capacity", Result.RATIOTYPE, cap, n, cap, cap_sq, n))
+        res.add_result(Result.from_batch("min_sinr_dB", Result.RATIOTYPE, gf("min_sinr_dB_sum"), n, gf("min_sinr_dB_sum"),
+                                         gf("min_sinr_dB_sq"), n))
         hist = [int(round(gf("sinr_h%d" % i))) for i in range(self.hist_bins + 2)]
         res.add_result(Result.from_histogram("sinr_histogram", hist))
         return res

@@ -25,7 +25,7 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 PREFIXES = ("k_run_", "k_link_walk", "k_mimo_filters", "k_tdl_symbol_polys", "k_mimo_tdl_symbol_polys", "k_mimo_flat_", "k_ia_solve_links",
             "k_ia_link", "k_bd_solve_links", "k_bd_link", "k_comp_solve_links", "k_comp_link", "k_ofdm_mod_1024_mfma", "k_ofdm_demod_1024_mfma", "k_jakes_blocks",
             "k_jakes_mfma", "k_cazac_estimate", "k_cazac_cancel", "k_chanest", "k_ls_estimate", "k_mmse_estimate",
-            "k_pilot_mse", "k_codebook", "k_quantize", "k_iagl_", "k_mimo_pilot_", "k_mimo_large_", "k_indoor_")
+            "k_pilot_mse", "k_codebook", "k_quantize", "k_iagl_", "k_mimo_pilot_", "k_mimo_large_", "k_indoor_", "k_hex_")
 KEYS = (".vgpr_count", ".agpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count",
         ".private_segment_fixed_size", ".group_segment_fixed_size", ".max_flat_workgroup_size")
 
@@ -74,6 +74,7 @@ DEFAULT = [
     r"k_mimo_pilot_",                                  # the flat Blast link with pilot-estimated CSI (pipeline_mimo_pilot.hip)
     r"k_mimo_large_",                                  # the large-array Blast link on the matrix cores (pipeline_mimo_large.hip)
     r"k_indoor_",                                      # the indoor SINR operator and user drops (pipeline_indoor.hip)
+    r"k_hex_",                                         # the hexagonal-cluster operator and user drops (pipeline_hex.hip)
     r"k_bd_link<", r"k_mimo_flat_", r"k_link_walk<",    # (round 6: the packed walk for an even number of columns >= 128; k_ia_link / k_bd_link otherwise)
 ]
 
