@@ -679,7 +679,33 @@ int mcle_run_ia(mcle_ctx* ctx, int dtype, const mcle_ia_cfg* cfg, uint64_t seed,
 /* ---- a15: ClosedFormIASolver.solve (ia/algorithms.py:194-265) on injected channels, f64 only:
  *      d_bigH [batch][6][6] (MultiUserChannelMatrix.big_H, K = 3, 2x2) -> precoders d_F
  *      [batch][3][2] (full_F, P = 1), receive filters d_U [batch][3][2] (full_W_H), per-user SINR
- *      d_sinr [batch][3] and sum capacity d_capacity [batch] (both may be NULL) ------------------ */
+ *      d_sinr [batch][3] and sum capacity d_capacity [batch] (both may be NULL).
+ *      d_skipped [batch] (may be NULL; both entry points): 1 iff the realization has no solution to report -- one of the four
+ *      inverted cross channels (H31, H12, H23, H32) is singular relative to its entries (|det| <= 1e-140 |H|_F^2; an
+ *      iterative solver: a matrix it inverts on the way), the alignment is infeasible for a user (|W_k^H H_kk F_k| <=
+ *      2^-33 |W_k| |H_kk|_F |F_k|: the wanted signal lies in the interference subspace, e.g. with every block diagonal), or
+ *      an output is not finite.  The other outputs of such a realization are unspecified (they may be NaN); the fused
+ *      pipelines count it in n_skipped.  Every other realization has finite outputs with U_k H_kk F_k = 1.
+ *      A 2x2 eigenproblem with a repeated eigenvalue (a multiple of the identity to 2^-44: E with every cross channel equal,
+ *      H_kk^H H_kk of a unitary direct channel under MCLE_IA_INIT_SVD, two orthogonal interferers of equal norm) HAS an
+ *      answer: the canonical basis, e1 for the first (smaller) and e2 for the second (larger) eigenvalue, as LAPACK returns;
+ *      MCLE_IA_INIT_SVD then starts from e1, the first right singular vector, as the reference does.  mcle_ia_closed_form
+ *      and the iterative solvers return that answer.  The fused pipelines' closed-form solve (mcle_run_ia and
+ *      mcle_run_ia_quantized with MCLE_IA_CLOSED_FORM) keeps its inlined body and FLAGS a realization whose E is a multiple
+ *      of the identity, or whose chosen candidate is infeasible beside a feasible one, instead of answering it.
+ *      Ties: the closed form keeps the first candidate unless the second one's capacity is strictly larger.  Where the two
+ *      capacities agree to rounding -- real channels whose E has a complex-conjugate eigenvalue pair: the candidates are
+ *      conjugates of one another -- the capacity is that of both and F, U are those of either one; which, rounding decides,
+ *      here as in the reference.  Conditioning: the results are held to 16 x max(the f64 reference's own error, the
+ *      measured sensitivity of the answer x 2^-52) (DESIGN.md "IA 2x2 envelope").  In mcle_ia_closed_form an
+ *      ill-conditioned H31 (|det| < 2^-12 |H31|_F^2) does not enter: H31 F0 is then taken as H32 N F0 / lambda, F0 being an
+ *      eigenvector of H31^-1 H32 N.  The other three inverted cross channels (H12, H23, H32), and H31 in the fused
+ *      pipelines, enter with their condition number (about cond x 2^-52); nothing is flagged for conditioning short of
+ *      the singularity above.
+ *      Scale: H -> c H with noise_var -> c^2 noise_var is the same problem.  The closed form holds it while |H|^4 is
+ *      representable (tested at c = 2^-250 ... 2^250); the iterative solvers form fourth powers of the entries and hold it
+ *      while |H|^8 is (tested at 2^-100 ... 2^100; at 2^+-250 they flag every realization).
+ *      An empty batch needs no arrays. ------------------------------------------------------------ */
 int mcle_ia_closed_form(mcle_ctx* ctx, const void* d_bigH, double noise_var, void* d_F, void* d_U,
                         double* d_sinr, double* d_capacity, uint32_t* d_skipped, size_t batch);
 /* Iterative solvers (solver = MCLE_IA_ALT_MIN / MIN_LEAKAGE / MAX_SINR / MMSE) from injected initial precoders
@@ -693,7 +719,8 @@ int mcle_ia_closed_form(mcle_ctx* ctx, const void* d_bigH, double noise_var, voi
  * iteration ends badly conditioned -- a stream in outage, an eighth or more of a realization's symbols wrong -- the
  * rounding-level difference is amplified over the iterations and decisions at near-ties may differ: bound asserted by
  * tests/test_gpu_fuzz.py on such realizations: |symbol errors - reference's| <= max(2, 2 %), |bit errors| <= max(8, 4 %);
- * every other realization is exact.  The closed-form solver (mcle_ia_closed_form) has no such caveat. */
+ * every other realization is exact.  The closed-form solver (mcle_ia_closed_form) iterates nothing and has no such
+ * amplification; its own caveats are the tie rule and the conditioning rule above (tests/test_gpu_ia3_envelope.py). */
 int mcle_ia_iterative(mcle_ctx* ctx, int solver, int initialize_with, const void* d_bigH,
                       const void* d_F_init, double noise_var, int max_iterations, double relative_factor,
                       void* d_F, void* d_U, double* d_sinr, double* d_capacity, uint32_t* d_iterations,

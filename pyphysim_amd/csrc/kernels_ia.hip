@@ -54,9 +54,23 @@ __device__ __forceinline__ V2 mvec(const M2& p, const V2& v) {
     r.y = cadd(cmul(p.c, v.x), cmul(p.d, v.y));
     return r;
 }
+// An opaque copy for the validity checks (singular, scalar, feasible).  They square the numbers the solve squares; sharing
+// such a product gives it a second use, the compiler then no longer contracts it into the solve's sums, and the last
+// bits of every generic result move.  Through the copy the solve compiles to what it was without the checks.
+__device__ __forceinline__ double opq(double x) {
+    asm("" : "+v"(x));
+    return x;
+}
+__device__ __forceinline__ double cabs2_opq(cd z) {
+    const double x = opq(z.x), y = opq(z.y);
+    return x * x + y * y;
+}
 __device__ __forceinline__ M2 minv(const M2& p, bool& ok) {
     const cd det = csub(cmul(p.a, p.d), cmul(p.b, p.c));
-    ok = ok && (cabs2(det) > 1e-280);
+    // singular relative to the entries: |det| <= 1e-140 |p|_F^2 (two divisions: neither |det|^2 nor |p|_F^4 need be
+    // representable together, so a channel scaled by 2^-250 -- |det|^2 = 3e-301 -- is not refused; a zero matrix is)
+    const double n2 = cabs2_opq(p.a) + cabs2_opq(p.b) + cabs2_opq(p.c) + cabs2_opq(p.d);
+    ok = ok & (cabs2(det) / n2 / n2 > 1e-280);
     M2 r;
     r.a = cdiv_(p.d, det);
     r.b = cdiv_(mk<double>(-p.b.x, -p.b.y), det);
@@ -80,14 +94,27 @@ __device__ __forceinline__ V2 lapack_normalize(V2 v) {
     v.y = cmul(v.y, ph);
     return v;
 }
-// eigenvector of E for eigenvalue lam: the better conditioned of the two rows of (E - lam I)
-__device__ __forceinline__ V2 eigvec2(const M2& E, cd lam) {
+// eigenvector of E for eigenvalue lam: the better conditioned of the two rows of (E - lam I).  Where E is a multiple of
+// the identity to rounding (|b|, |c|, |a - d| <= 2^-44 |a|) every vector is an eigenvector and both rows hold nothing but
+// the rounding of E: the canonical basis, as LAPACK returns it -- e1 for which = 0, e2 for which = 1.  The test reads E
+// and not the rows: of a general E the two eigenvalues come out of a square root of tr^2 - 4 det, which leaves
+// sqrt(rounding) = 1e-8 |a| in the rows of a matrix that is the identity to 1e-16.
+__device__ __forceinline__ bool is_scalar2(const M2& E) {
+    const cd ea = mk<double>(opq(E.a.x), opq(E.a.y)), ed = mk<double>(opq(E.d.x), opq(E.d.y));
+    return fmax(fmax(cabs2_opq(E.b), cabs2_opq(E.c)), cabs2(csub(ea, ed))) <= 0x1p-88 * cabs2(ea);
+}
+__device__ __forceinline__ V2 eigvec2(const M2& E, cd lam, int which) {
     const V2 v1{E.b, csub(lam, E.a)};
     const V2 v2{csub(lam, E.d), E.c};
     const double n1 = cabs2(v1.x) + cabs2(v1.y), n2 = cabs2(v2.x) + cabs2(v2.y);
-    return lapack_normalize(n1 >= n2 ? v1 : v2);
+    V2 v = lapack_normalize(n1 >= n2 ? v1 : v2);
+    // (a select after the fact, not a branch around the rows: the rows are sums the compiler contracts with the products
+    //  that formed lam, and only within one basic block)
+    const bool scalar = is_scalar2(E);
+    v.x = mk<double>(scalar ? (which ? 0.0 : 1.0) : v.x.x, scalar ? 0.0 : v.x.y);
+    v.y = mk<double>(scalar ? (which ? 1.0 : 0.0) : v.y.x, scalar ? 0.0 : v.y.y);
+    return v;
 }
-
 struct IaSolution {
     V2 F[3];    // precoders (column vectors, unit norm)
     V2 U[3];    // receive filters full_W_H (row vectors)
@@ -95,15 +122,62 @@ struct IaSolution {
     double capacity;
     bool ok;
 };
+// every number of the solution finite: an infeasible alignment (W^H H_kk F_k = 0) divides U by zero, and an infinite U
+// gives sinr = 0 and a capacity that is a number
+__device__ __forceinline__ bool ia_finite(const IaSolution& s) {
+    double acc = s.capacity;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        acc += fabs(s.F[k].x.x) + fabs(s.F[k].x.y) + fabs(s.F[k].y.x) + fabs(s.F[k].y.y) + fabs(s.U[k].x.x) + fabs(s.U[k].x.y) +
+               fabs(s.U[k].y.x) + fabs(s.U[k].y.y) + s.sinr[k];
+    return acc - acc == 0.0;     // false for inf and NaN
+}
+// A solution to report: every number finite, and the alignment feasible for every user -- |W^H H_kk F_k| > 2^-33 |W| |H_kk|_F
+// |F_k|, read off the finished filter as |U_k| |H_kk|_F |F_k| < 2^33 (U = W^H / (W^H H_kk F_k)).  Below that the wanted signal
+// lies in the interference subspace (exactly, or to the rounding of the product: 2^-52 |H_kk|) and U is rounding noise.
+// A pass over the results, after the solve and through opaque copies: the solve itself compiles to what it was.
+__device__ __forceinline__ bool ia_valid(const M2 (&H)[3][3], const IaSolution& s) {
+    bool ok = ia_finite(s);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const M2& h = H[k][k];
+        const double hn = cabs2_opq(h.a) + cabs2_opq(h.b) + cabs2_opq(h.c) + cabs2_opq(h.d);
+        ok = ok & ((cabs2_opq(s.U[k].x) + cabs2_opq(s.U[k].y)) * hn * (cabs2_opq(s.F[k].x) + cabs2_opq(s.F[k].y)) < 0x1p66);
+    }
+    return ok;
+}
 
-// H[k][l]: channel from transmitter l to receiver k
+// H31 is ill conditioned: |det| < 2^-12 |H31|_F^2 (condition number above about 4e3; one Rayleigh draw in 1e7).  Its own
+// arithmetic on opaque copies, like every check here.
+__device__ __forceinline__ bool ia_ill(const M2& p) {
+    const cd a = mk<double>(opq(p.a.x), opq(p.a.y)), b = mk<double>(opq(p.b.x), opq(p.b.y));
+    const cd c = mk<double>(opq(p.c.x), opq(p.c.y)), d = mk<double>(opq(p.d.x), opq(p.d.y));
+    const double n2 = cabs2(a) + cabs2(b) + cabs2(c) + cabs2(d);
+    return cabs2(csub(cmul(a, d), cmul(b, c))) / n2 / n2 < 0x1p-24;
+}
+
+// H[k][l]: channel from transmitter l to receiver k.
+// ILL (H31 ill conditioned; N = H12^-1 H13 H23^-1 H21, lam = F0's eigenvalue): F0 is an eigenvector of E = H31^-1 (H32 N),
+// so H31 F0 = H32 N F0 / lam.  F0 then lies close to the weak right singular vector of H31, and H31 F0 -- the direction
+// receiver 3 nulls and user 2 aligns with -- is the small difference of two products: the rounding of F0 alone moves it
+// by cond x 2^-52 (graded 1e6: capacity off by 2e-10).  H32 N F0 / lam has no such cancellation and stands in for it.
+template <bool ILL>
 __device__ __forceinline__ void ia_candidate(const M2 (&H)[3][3], const M2& invH32, const M2& invH23, V2 F0,
-                                             double nv, IaSolution& s) {
+                                             double nv, IaSolution& s, const M2* N = nullptr, cd lam = cd{0.0, 0.0}) {
     s.ok = true;
     s.F[0] = vnormalize(F0);
-    s.F[1] = vnormalize(mvec(invH32, mvec(H[2][0], F0)));
+    V2 h31f, a2;
+    if constexpr (ILL) {
+        const V2 mf = mvec(H[2][1], mvec(*N, F0));
+        h31f = V2{cdiv_(mf.x, lam), cdiv_(mf.y, lam)};
+        a2 = h31f;                               // (only its direction is used)
+    } else {
+        h31f = mvec(H[2][0], F0);
+    }
+    s.F[1] = vnormalize(mvec(invH32, h31f));
     s.F[2] = vnormalize(mvec(invH23, mvec(H[1][0], F0)));
-    const V2 a[3] = {mvec(H[0][1], s.F[1]), mvec(H[1][0], s.F[0]), mvec(H[2][0], s.F[0])};
+    if constexpr (!ILL) a2 = mvec(H[2][0], s.F[0]);
+    const V2 a[3] = {mvec(H[0][1], s.F[1]), mvec(H[1][0], s.F[0]), a2};
     s.capacity = 0.0;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -126,9 +200,19 @@ __device__ __forceinline__ void ia_candidate(const M2 (&H)[3][3], const M2& invH
     }
 }
 
-// ia_closed_form: not inlined, one compiled body serves the operator kernel and the iterative solver's 'closed_form'
-// start.  The pipeline's solve kernel inlines the same body (ia_closed_form_inl): behind a call, H and the solution
-// live in scratch (1.3 KB per lane), inlined they stay in registers.
+// eigenvector of a general E without the scalar test: the text the pipeline's solve has always compiled
+__device__ __forceinline__ V2 eigvec2_plain(const M2& E, cd lam) {
+    const V2 v1{E.b, csub(lam, E.a)};
+    const V2 v2{csub(lam, E.d), E.c};
+    const double n1 = cabs2(v1.x) + cabs2(v1.y), n2 = cabs2(v2.x) + cabs2(v2.y);
+    return lapack_normalize(n1 >= n2 ? v1 : v2);
+}
+
+// The closed form as the fused pipeline's solve kernel inlines it (k_ia_solve_links: inlined, H and the solution stay in
+// registers).  Its arithmetic and its choice are the text they have always been, so every realization that had an answer
+// keeps its bits; what is new comes after the choice and only reads: the solution is flagged unless ia_valid.  A
+// realization this body cannot answer -- E a multiple of the identity (its eigenvectors come out NaN), a chosen candidate
+// that is infeasible beside one that is not -- is therefore FLAGGED here; ia_closed_form below answers it.
 __device__ __forceinline__ IaSolution ia_closed_form_inl(const M2 (&H)[3][3], double nv) {
     bool ok = true;
     const M2 i31 = minv(H[2][0], ok), i12 = minv(H[0][1], ok), i23 = minv(H[1][2], ok), i32 = minv(H[2][1], ok);
@@ -139,15 +223,52 @@ __device__ __forceinline__ IaSolution ia_closed_form_inl(const M2 (&H)[3][3], do
     const cd disc = csqrt_(csub(cmul(tr, tr), cscale(det, 4.0)));
     const cd l0 = cscale(cadd(tr, disc), 0.5), l1 = cscale(csub(tr, disc), 0.5);
     IaSolution s0, s1;
-    ia_candidate(H, i32, i23, eigvec2(E, l0), nv, s0);
-    ia_candidate(H, i32, i23, eigvec2(E, l1), nv, s1);
+    ia_candidate<false>(H, i32, i23, eigvec2_plain(E, l0), nv, s0);
+    ia_candidate<false>(H, i32, i23, eigvec2_plain(E, l1), nv, s1);
     // strict '>' keeps the first candidate on ties, like algorithms.py:250; LAPACK's eigenvalue
     // ORDER is not reproduced (it only matters on exact ties)
     IaSolution s = (s1.capacity > s0.capacity) ? s1 : s0;
-    s.ok = ok && (s.capacity == s.capacity);
+    s.ok = ok & ia_valid(H, s);
     return s;
 }
-__device__ __noinline__ IaSolution ia_closed_form(const M2 (&H)[3][3], double nv) { return ia_closed_form_inl(H, nv); }
+
+// The closed form with every special case answered: E a multiple of the identity (canonical basis), an ill-conditioned H31
+// (ia_candidate<true>), a candidate without a solution (it loses to one that has: the reference's `capacity > best` is
+// false for its NaN too).  Only ia_closed_form calls it, for the realizations that need it.
+__device__ __noinline__ IaSolution ia_closed_form_special(const M2 (&H)[3][3], double nv) {
+    bool ok = true;
+    const M2 i31 = minv(H[2][0], ok), i12 = minv(H[0][1], ok), i23 = minv(H[1][2], ok), i32 = minv(H[2][1], ok);
+    const M2 N = mmul(mmul(i12, H[0][2]), mmul(i23, H[1][0]));
+    const M2 E = mmul(mmul(i31, H[2][1]), N);
+    const cd tr = cadd(E.a, E.d);
+    const cd det = csub(cmul(E.a, E.d), cmul(E.b, E.c));
+    const cd disc = csqrt_(csub(cmul(tr, tr), cscale(det, 4.0)));
+    const cd l0 = cscale(cadd(tr, disc), 0.5), l1 = cscale(csub(tr, disc), 0.5);
+    const V2 f0 = eigvec2(E, l0, 0), f1 = eigvec2(E, l1, 1);
+    IaSolution s0, s1;
+    // (an eigenvalue 0 -- a rank-deficient H21 or H13 -- has no H32 N F0 / lam: the literal product then)
+    if (ia_ill(H[2][0]) && cabs2(l0) > 0.0 && cabs2(l1) > 0.0) {
+        ia_candidate<true>(H, i32, i23, f0, nv, s0, &N, l0);
+        ia_candidate<true>(H, i32, i23, f1, nv, s1, &N, l1);
+    } else {
+        ia_candidate<false>(H, i32, i23, f0, nv, s0);
+        ia_candidate<false>(H, i32, i23, f1, nv, s1);
+    }
+    s0.ok = ia_valid(H, s0);
+    s1.ok = ia_valid(H, s1);
+    IaSolution s = ((s1.ok & !s0.ok) | ((s1.ok == s0.ok) & (s1.capacity > s0.capacity))) ? s1 : s0;
+    s.ok = ok & s.ok;
+    return s;
+}
+
+// ia_closed_form: not inlined, one compiled body serves the operator kernel and the iterative solver's 'closed_form'
+// start (behind a call, H and the solution live in scratch, 1.3 KB per lane).  The generic realization takes the inlined
+// body above and keeps its bits; one that body flags, or whose H31 is ill conditioned, is solved again with every case.
+__device__ __noinline__ IaSolution ia_closed_form(const M2 (&H)[3][3], double nv) {
+    IaSolution s = ia_closed_form_inl(H, nv);
+    if (!s.ok | ia_ill(H[2][0])) s = ia_closed_form_special(H, nv);
+    return s;
+}
 
 // ---- iterative solvers on the same 2x2 / one-stream geometry ----------------------
 // Reference: ia/algorithms.py:802-883 (solve loop, _is_diff_significant :755-800), :1010-1129 (alternating
@@ -179,8 +300,8 @@ __device__ __forceinline__ void heig2(const M2& A, V2& v_small, V2& v_large) {
     const double half = 0.5 * (a - d);
     const double r = sqrt(half * half + cabs2(A.b));
     const double mid = 0.5 * (a + d);
-    v_small = eigvec2(A, mk<double>(mid - r, 0.0));
-    v_large = eigvec2(A, mk<double>(mid + r, 0.0));
+    v_small = eigvec2(A, mk<double>(mid - r, 0.0), 0);
+    v_large = eigvec2(A, mk<double>(mid + r, 0.0), 1);
 }
 __device__ __forceinline__ bool ia_diff_significant(const V2 (&Fo)[3], const V2 (&Fn)[3], double rel) {
     bool sig = false;
@@ -343,7 +464,7 @@ __device__ __forceinline__ int ia_iterate(const M2 (&H)[3][3], int algo, double 
             // first row of inv([H_kk F_k, C_k])
             const V2 a = mvec(H[k][k], F[k]);
             const cd det = csub(cmul(a.x, W[k].y), cmul(W[k].x, a.y));
-            ok = ok && (cabs2(det) > 1e-280);
+            ok = ok && (cabs2(det) / (cabs2_opq(a.x) + cabs2_opq(a.y)) > 1e-280);     // relative: C_k has unit norm
             Wh[k].x = cdiv_(W[k].y, det);
             Wh[k].y = cdiv_(mk<double>(-W[k].x.x, -W[k].x.y), det);
         } else {
@@ -414,8 +535,13 @@ __device__ __noinline__ IaSolution ia_iterative(const M2 (&H)[3][3], int algo, d
             g.d = mk<double>(cabs2(h.b) + cabs2(h.d), 0.0);
             g.b = cadd(cmul(cconj(h.a), h.b), cmul(cconj(h.c), h.d));
             g.c = cconj(g.b);
-            V2 lo;
-            heig2(g, lo, F[k]);
+            // (equal singular values -- an identity or unitary direct channel -- keep their order in LAPACK's SVD, and
+            //  the reference takes the first right singular vector: e1, which heig2 files under the smaller eigenvalue)
+            V2 lo, hi;
+            heig2(g, lo, hi);
+            const bool same = is_scalar2(g);
+            F[k].x = mk<double>(same ? lo.x.x : hi.x.x, same ? lo.x.y : hi.x.y);
+            F[k].y = mk<double>(same ? lo.y.x : hi.y.x, same ? lo.y.y : hi.y.y);
         }
     } else if (init == IA_INIT_ALT_MIN) {
         V2 Wha[3];
@@ -427,7 +553,7 @@ __device__ __noinline__ IaSolution ia_iterative(const M2 (&H)[3][3], int algo, d
     runned = ia_iterate(H, algo, nv, max_iter, rel, F, Wh, ok, W_init);
     IaSolution s;
     ia_finish(H, F, Wh, nv, s);
-    s.ok = ok && (s.capacity == s.capacity);
+    s.ok = ok & ia_valid(H, s);
     return s;
 }
 
@@ -785,7 +911,8 @@ extern "C" {
 
 int mcle_ia_closed_form(mcle_ctx* ctx, const void* d_bigH, double noise_var, void* d_F, void* d_U, double* d_sinr,
                         double* d_capacity, uint32_t* d_skipped, size_t batch) {
-    MCLE_REQUIRE(ctx != nullptr && d_bigH != nullptr && d_F != nullptr && d_U != nullptr, "null argument");
+    // (an empty batch has no arrays: nothing to dereference)
+    MCLE_REQUIRE(ctx != nullptr && (batch == 0 || (d_bigH != nullptr && d_F != nullptr && d_U != nullptr)), "null argument");
     MCLE_REQUIRE(noise_var >= 0.0, "noise variance must be non-negative");
     if (batch == 0) return MCLE_OK;
     int rc = ctx->bind();
@@ -800,7 +927,7 @@ int mcle_ia_closed_form(mcle_ctx* ctx, const void* d_bigH, double noise_var, voi
 int mcle_ia_iterative(mcle_ctx* ctx, int solver, int initialize_with, const void* d_bigH, const void* d_F_init,
                       double noise_var, int max_iterations, double relative_factor, void* d_F, void* d_U,
                       double* d_sinr, double* d_capacity, uint32_t* d_iterations, uint32_t* d_skipped, size_t batch) {
-    MCLE_REQUIRE(ctx != nullptr && d_bigH != nullptr && d_F_init != nullptr && d_F != nullptr && d_U != nullptr,
+    MCLE_REQUIRE(ctx != nullptr && (batch == 0 || (d_bigH != nullptr && d_F_init != nullptr && d_F != nullptr && d_U != nullptr)),
                  "null argument");
     MCLE_REQUIRE(solver >= MCLE_IA_ALT_MIN && solver <= MCLE_IA_MMSE, "solver must be one of the iterative MCLE_IA_*");
     MCLE_REQUIRE(noise_var >= 0.0, "noise variance must be non-negative");
